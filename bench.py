@@ -12,7 +12,9 @@ independent: ranks own disjoint global env-id ranges, there is no data-path coll
 Synthetic actions (Philox keyed on (seed, global env id, step)) are generated on the device BEFORE the
 timed region, so inputs are resident in HBM when timing starts.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  A plain run measures the headline only; --full adds everything
+else the line can carry (further timed regions, the preset-fast side measurement, BASELINE's sharded configs on > 1 GPU, the CPU baseline,
+the state sanity check, the HDF5 self-test).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -75,6 +77,47 @@ def kernel_sha16():
     h.update(repr((hipbuild.FLAGS, hipbuild.UNITS)).encode())
     return h.hexdigest()[:16]
 
+
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs: at most this much in all (npy headers included)
+DUMP_FRAME_ENVS = 16            # frames (obs both): both frames of this many envs, 2 x 16 x 240x320x3 float32 = 29.5 MB
+
+
+def dump_outputs(sim, out_dir):
+    """What the last step returned to a caller of lcr_step, as out_dir/<name>.npy in float32, env-major: the observations, reward and episode
+    flags of every env, the terminal observations of the envs it reset (zeros elsewhere) and, with frames, both frames of a fixed seeded
+    sample of envs (frame_env_ids.npy).  Beyond the size budget the per-env arrays are a fixed seeded sample of envs as well (env_ids.npy)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = sim.n
+    budget = DUMP_BYTES
+    files = {}
+    if sim.image_front is not None:
+        fids = np.sort(np.random.default_rng(1).choice(n, min(n, DUMP_FRAME_ENVS), replace=False))
+        files["image_front"] = sim.read_rows(sim.image_front, fids).astype(np.float32)
+        files["image_top"] = sim.read_rows(sim.image_top, fids).astype(np.float32)
+        files["frame_env_ids"] = fids.astype(np.float64)
+        budget -= sum(a.nbytes for a in files.values())
+    per_env = {"arm_qpos": sim.arm_qpos, "arm_qvel": sim.arm_qvel}
+    if sim.aux_pos is not None:
+        per_env[sim.aux_name] = sim.aux_pos
+    per_env[sim.cube_name] = sim.cube_pos
+    for k in ("reward", "terminated", "truncated", "is_success", "did_reset", "terminal_obs"):
+        per_env[k] = getattr(sim, k)
+    per_env = {k: v.numpy().reshape(-1, n).T.astype(np.float32) for k, v in per_env.items()}   # [k][N] -> (N, k)
+    per_env["terminal_obs"][per_env["did_reset"][:, 0] == 0] = 0.0   # (only the envs the step reset have terminal observations)
+    budget -= 4096 * (len(files) + len(per_env) + 1)   # (npy headers)
+    row_bytes = sum(a.shape[1] for a in per_env.values()) * 4
+    ids = None
+    if n * row_bytes > budget:
+        ids = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))
+        files["env_ids"] = ids.astype(np.float64)
+    for k, a in per_env.items():
+        a = a if ids is None else a[ids]
+        files[k] = a[:, 0] if a.shape[1] == 1 else a
+    for k, a in files.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(files)
 
 
 def cpu_baseline(task, action_mode, budget_s=12.0):
@@ -169,20 +212,27 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=65536)
     ap.add_argument("--workload", default="ReachCube-v0", choices=sorted(WORKLOADS))
     ap.add_argument("--config", type=int, default=0, choices=[0] + sorted(CONFIGS), help="BASELINE.json configs[N-1] at its per-GPU size (overrides --workload / --envs-per-gpu / --obs)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions in total (the first is the contract's K steps; the rest give the median SURVEY.md 8(d) asks for)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: further timed regions (--repeats), the preset-fast side measurement, BASELINE's sharded configs on > 1 GPU, "
+                         "the CPU baseline, the state sanity check and the HDF5 self-test")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (observations, reward, episode flags; frames of a fixed sample of envs) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: timed regions in total (the first is the contract's K steps; the rest give the median SURVEY.md 8(d) asks for)")
     ap.add_argument("--arm-collision", type=int, default=1, help="0: round-1 contact model (finger tips only), for like-for-like comparison")
     ap.add_argument("--preset", default="faithful", choices=["faithful", "fast"],
                     help="faithful (default, the headline): the reference's contact model solved by Newton's method; fast: rounds 1-4 (four block projected-gradient sweeps)")
     ap.add_argument("--pgs-iters", type=int, default=None, help="preset fast only: sweeps per substep (default 4; < 0: swept to a tolerance)")
-    ap.add_argument("--no-fast-side", action="store_true", help="skip the side measurement of preset fast that a faithful run reports beside its headline")
+    ap.add_argument("--no-fast-side", action="store_true", help="--full: skip the side measurement of preset fast that a faithful run reports beside its headline")
     ap.add_argument("--obs", default="state", choices=["state", "both"], help="both: also ray-cast the two 240x320x3 observation frames per env")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-all-tasks", action="store_true", help="BASELINE.md B2: also time the CPU oracle on every workload (adds ~1 min)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (nccl) even for a single rank (tests the N>1 code path on one GPU)")
     ap.add_argument("--prewarm-ms", type=float, default=60.0, help="untimed spin of the step kernel before the contract's warm-up so that the timed region runs at steady clocks (0 disables)")
-    ap.add_argument("--sharded-configs", type=int, default=-1, help="1: also time BASELINE configs 4 and 5 at their per-GPU shard size (extra object, never the headline); default: on when --gpus > 1 and no --config")
+    ap.add_argument("--sharded-configs", type=int, default=-1, help="1: also time BASELINE configs 4 and 5 at their per-GPU shard size (extra object, never the headline); default: on with --full when --gpus > 1 and no --config")
     ap.add_argument("--calibrate", type=int, default=0, help="after timing, launch the known-byte-count copy kernel this many times (PMC calibration)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config:
         args.workload, args.envs_per_gpu, args.obs = CONFIGS[args.config]
 
@@ -247,14 +297,18 @@ def main():
 
     # clock ramp: with the driver's --warmup 5 the contract region used to start ~1.5 ms after the first launch and came out 6 % slower
     # than the regions after it; an untimed spin (not part of W or K) brings the GPU to steady clocks first
+    # it runs for a time, not a number of steps: the state it leaves behind is put back, so that the W + K steps see the same inputs in every run
     prewarm_steps = 0
     if args.prewarm_ms > 0:
+        ck = sim.get_state()
         t0 = time.perf_counter()
         while (time.perf_counter() - t0) * 1e3 < args.prewarm_ms:
             for i in range(16):
                 sim.step_device(bufs[(prewarm_steps + i) % ring].ptr)
             sim.sync()
             prewarm_steps += 16
+        sim.set_state(**ck)   # (a checkpoint of lcr_get_state restores exactly, carried constraint forces included)
+        del ck
     for i in range(args.warmup):
         sim.step_device(bufs[i % ring].ptr)
     ev = {}
@@ -268,9 +322,12 @@ def main():
 
     dt, _ = sharding.timed_region(run, args.steps, dist=dist, device_sync=torch.cuda.synchronize, tensor_device="cuda" if backend == "nccl" else "cpu")
     ev_ms = ev["ms"]
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(sim, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"))
     # further regions of the same K steps (HIP events on the launch stream, this rank only): median of `repeats`
     rep_ms = [ev_ms / args.steps]
-    for r in range(max(args.repeats, 1) - 1):
+    for r in range(max(args.repeats, 1) - 1 if args.full else 0):
         sim.timer_begin()
         for i in range(args.steps):
             sim.step_device(bufs[(args.warmup + i + 7 * (r + 1)) % ring].ptr)
@@ -278,7 +335,7 @@ def main():
 
     # the same workload under preset "fast" (rounds 1-4: four sweeps, fewer contact rows), reported BESIDE the headline, never as it: same barrier + max-over-ranks timing
     fast_side = None
-    if args.preset == "faithful" and not args.no_fast_side:
+    if args.full and args.preset == "faithful" and not args.no_fast_side:
         jf = job_kwargs(args.config, n, world, "fast", None)
         sim_f = VecSim(task, n, device=local_rank, env_id_offset=sharding.shard_offset(n, rank), observation_mode=args.obs, action_mode=action_mode,
                        preset="fast", base_seed=0, arm_collision=args.arm_collision, **jf)
@@ -302,7 +359,7 @@ def main():
     # BASELINE.json's sharded shapes (configs 4 and 5: PickPlace-ee 4 x 32 768, Stack + frames 8 x 32 768) at their per-GPU size, so that
     # a multi-GPU run of the default command line also covers them; same barrier + max-over-ranks timing, reported beside the headline
     sharded = None
-    want_sharded = args.sharded_configs == 1 or (args.sharded_configs < 0 and world > 1 and not args.config)
+    want_sharded = args.sharded_configs == 1 or (args.sharded_configs < 0 and args.full and world > 1 and not args.config)
     if want_sharded:
         sharded = {}
         for cid in (4, 5):
@@ -333,11 +390,13 @@ def main():
     if args.calibrate:
         sim.sync()
 
-    # sanity: the timed work must have produced finite state and episodes must have cycled
-    st = sim.get_state()
     import numpy as np
 
-    finite = bool(np.isfinite(st["qpos"]).all() and np.isfinite(st["qvel"]).all())
+    # sanity: the timed work must have produced finite state and episodes must have cycled
+    finite = None
+    if args.full:
+        st = sim.get_state()
+        finite = bool(np.isfinite(st["qpos"]).all() and np.isfinite(st["qvel"]).all())
 
     if rank == 0:
         kern_ms = ev_ms / args.steps
@@ -384,8 +443,6 @@ def main():
                 "arm_collision": bool(args.arm_collision),
                 "kernel_sha16": sha,
             },
-            "repeats": {"ms_per_step": rep_ms, "median_ms_per_step": float(np.median(rep_ms)),
-                        "median_value": n * world / (float(np.median(rep_ms)) * 1e-3)},
             "roofline": {
                 "bound": "hbm",
                 "achieved": achieved,
@@ -410,10 +467,15 @@ def main():
                          "not the sum of the two kernels' durations"),
                 "frames_overlap_step_kernel": bool(args.obs != "state" and os.environ.get("LCR_RENDER_OVERLAP", "1") != "0"),
             },
-            "state_finite": finite,
             "calibration_bytes_per_launch": calib_bytes or None,
-            "prewarm": {"ms": args.prewarm_ms, "steps": prewarm_steps, "note": "untimed spin before the W warm-up steps (steady clocks); not part of W or K"},
+            "prewarm": {"ms": args.prewarm_ms, "steps": prewarm_steps,
+                        "note": "untimed spin before the W warm-up steps (steady clocks), the state restored after it; not part of W or K"},
         }
+        if args.full:
+            out["repeats"] = {"ms_per_step": rep_ms, "median_ms_per_step": float(np.median(rep_ms)), "median_value": n * world / (float(np.median(rep_ms)) * 1e-3)}
+            out["state_finite"] = finite
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if fast_side is not None:
             out["preset_fast"] = fast_side
         if sharded is not None:
@@ -460,7 +522,7 @@ def main():
                 })
         except Exception as exc:   # (a missing profile file must not take the bench line down -- but it is said, not swallowed: VERDICT r5 weak #10a)
             out.setdefault("valu", {})["note"] = f"PMC-derived VALU figures not echoed: {exc!r}"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(task, action_mode)
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if args.cpu_all_tasks:
@@ -472,12 +534,13 @@ def main():
                 out["cpu_baseline"]["mujoco_opportunistic"] = mujoco_opportunistic.run(300)
             except Exception as e:
                 out["cpu_baseline"]["mujoco_opportunistic"] = {"status": "reference MuJoCo unavailable", "error": repr(e)}
-        try:  # a real .hdf5 episode file through h5py or, without it, the HDF5 C library (recorder.backend())
-            from gym_lowcostrobot_amd import recorder
+        if args.full:
+            try:  # a real .hdf5 episode file through h5py or, without it, the HDF5 C library (recorder.backend())
+                from gym_lowcostrobot_amd import recorder
 
-            out["hdf5"] = recorder.hdf5_selftest()
-        except Exception as e:
-            out["hdf5"] = {"status": "selftest failed", "error": repr(e)}
+                out["hdf5"] = recorder.hdf5_selftest()
+            except Exception as e:
+                out["hdf5"] = {"status": "selftest failed", "error": repr(e)}
         print(json.dumps(out), flush=True)
     for b in bufs:
         sim.free(b)

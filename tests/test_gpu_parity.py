@@ -641,7 +641,7 @@ def test_bench_two_ranks_on_one_gpu(hip_lib):
     env = dict(os.environ, LCR_BENCH_DIST_BACKEND="gloo", LCR_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29617", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-           "--envs-per-gpu", "4096", "--no-cpu-baseline"]
+           "--envs-per-gpu", "4096", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
