@@ -11,7 +11,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LCR_LIB_PATH") or os.path.join(_HERE, "liblcr_hip.so")  # override: A/B builds of the same ABI
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 NWARM = 124   # LCR_NWARM: floats per env of carried constraint forces (layout: include/lcr.h)
 TASKS = {"reach": 0, "lift": 1, "push": 2, "pick_place": 3, "stack": 4, "push_loop": 5}
 ACTION_MODES = {"joint": 0, "ee": 1}
@@ -20,6 +20,7 @@ REWARD_TYPES = {"sparse": 0, "dense": 1}
 STEP_KERNELS = {"auto": 0, "single": 1, "coop": 2}   # lcr_config.step_kernel
 SOLVERS = {"pgs": 0, "newton": 1}                     # lcr_config.solver
 PRESETS = {"faithful": 0, "fast": 1}                  # lcr_config_preset
+COOP_SHARE = {None: 0, "owner": 1, "shared": 2, "handoff": 3}   # lcr_config.coop_share (one-cube Newton kernel; bit-identical results)
 PROFILE_MODES = {None: None, "wave_cycles": 2, "phase_cycles": 3}   # lcr_config.diagnostics values 2, 3 (per-wave cycle read-back; see include/lcr.h)
 COMPAT_ZERO_QVEL_ON_RESET = 1
 COMPAT_COLD_SOLVE_EACH_STEP = 2   # contact solver starts every control step from zero forces (default: forces carried across steps)
@@ -73,6 +74,7 @@ class LcrConfig(ctypes.Structure):
         ("finger_floor_condim", ctypes.c_int32),
         ("newton_tol", ctypes.c_double),
         ("ls_tol", ctypes.c_double),
+        ("coop_share", ctypes.c_int32),    # ABI v6: COOP_SHARE
     ]
 
 

@@ -208,6 +208,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     if (cfg->pgs_iters < 0 && !(cfg->pgs_tol > 0)) return fail(LCR_ERR_INVALID, "pgs_tol must be positive in converged mode (pgs_iters < 0)");
     if (cfg->finger_cube_condim != 0 && cfg->finger_cube_condim != 4 && cfg->finger_cube_condim != 6) return fail(LCR_ERR_INVALID, "finger_cube_condim must be 4 or 6");
     if (cfg->cc_points != 0 && cfg->cc_points != 4 && cfg->cc_points != 8) return fail(LCR_ERR_INVALID, "cc_points must be 4 or 8");
+    if (cfg->coop_share < 0 || cfg->coop_share > 3) return fail(LCR_ERR_INVALID, "coop_share must be 0 (default), 1 (owner only), 2 (shared) or 3 (always hand off)");
     if (cfg->cc_points == 8 && cfg->task != LCR_TASK_STACK) return fail(LCR_ERR_INVALID, "cc_points = 8 is the cube<->cube manifold of StackTwoCubes; this task has one cube");
     if (cfg->cc_points == 8 && cfg->pgs_iters < 0) return fail(LCR_ERR_UNSUPPORTED, "cc_points = 8 is implemented by the two-wave kernels, the converged solver mode (pgs_iters < 0) by the one-wave kernels");
     if (cfg->step_kernel < 0 || cfg->step_kernel > 2) return fail(LCR_ERR_INVALID, "step_kernel must be 0 (by task and job size), 1 (one wave per 64 envs) or 2 (two cooperating waves)");
@@ -397,6 +398,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
             D.newton = cfg->solver == LCR_SOLVER_NEWTON ? 1 : 0;
             D.newton_iters = cfg->newton_iters; D.ls_iters = cfg->ls_iters;
             D.newton_tol = (float)cfg->newton_tol; D.ls_tol = (float)cfg->ls_tol;
+            D.coop_share = cfg->coop_share == 0 ? 1 : cfg->coop_share - 1;   // (one-cube Newton kernel: who solves a wave's coupled envs; the bits do not depend on it)
             // coupled envs a wave of the Newton kernels solves cooperatively (lcr_newton_coop.h: four per pass, one per 16-lane row; StackTwoCubes' three-body patients one at a time)
             // before it falls back to the coupled SIMT solves: 8 with one cube (two passes; flat beyond), 16 with rails and for Stack (PushCubeLoop 5.52 / 4.91 / 4.90 ms at 4 / 8 / 16: the
             // fall-back's 12-dim SIMT iteration spills; Stack's 18-dim one 3 KB per lane: profiles/r06_coop_sweep.txt, r06_coop_sweep2.txt); measurement override: LCR_COOP_MAX (0: never)

@@ -72,6 +72,8 @@ struct LcrDev {
     int newton_iters, ls_iters;      // most Newton iterations per substep / most evaluations of phi' per line search
     float newton_tol, ls_tol;
     int coop_max;                    // Newton kernels: a wave solves up to this many coupled (arm on cube, cube on cube) envs one by one with all its lanes (lcr_newton_coop.h); more: the 12-dimensional SIMT solve
+    int coop_share;                  // one-cube Newton kernel: who solves a wave's coupled envs -- 0 the owning wave only, 1 any wave of the workgroup, the owner first (default),
+                                     // 2 never the owner (lcr_config.coop_share - 1; lcr_kernels.hip: CoopQueue)
 };
 
 // pinhole camera: position, world axes (camera looks along -Z), s = 2 tan(fovy/2) / height

@@ -84,6 +84,7 @@ class VecSim:
         newton_tol=None,
         ls_tol=None,
         finger_floor_condim=None,
+        coop_share=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -151,6 +152,9 @@ class VecSim:
             cfg.global_envs = int(global_envs)
         if cc_points is not None:   # StackTwoCubes: 4 (default) or 8 cube<->cube manifold points
             cfg.cc_points = int(cc_points)
+        if coop_share not in _capi.COOP_SHARE:   # one-cube Newton kernel: who solves a wave's coupled envs (None = shared; "owner" | "handoff": A/B runs, bit-identical)
+            raise ValueError(f"invalid coop_share {coop_share!r} (None | 'owner' | 'shared' | 'handoff')")
+        cfg.coop_share = _capi.COOP_SHARE[coop_share]
         self.cfg = cfg
         self.n = int(n_envs)
         self.device = int(device)

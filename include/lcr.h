@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LCR_ABI_VERSION 5
+#define LCR_ABI_VERSION 6
 
 typedef enum lcr_status {
     LCR_OK = 0,
@@ -134,6 +134,11 @@ typedef struct lcr_config {
                                   them.  0 = the preset's default.  6 is implemented by the Newton kernels (LCR_SOLVER_PGS with 6: LCR_ERR_UNSUPPORTED) */
     double newton_tol;         /* LCR_SOLVER_NEWTON: an env has converged when its Newton decrement -g'dx <= newton_tol^2 (1 + |a0|_M^2)   (1e-6) */
     double ls_tol;             /* ... its line search stops when |phi'(al)| <= ls_tol |phi'(0)|   (1e-2: MuJoCo's default ls_tolerance), plus a rounding floor 1e-5 (|M-part| + |force part|) of the two sums phi' is the difference of */
+    /* ABI v6 */
+    int32_t coop_share;        /* LCR_SOLVER_NEWTON, one-cube tasks: who solves the coupled envs of a wave (arm on its cube; four per pass with the whole wave).  The kernel runs
+                                  four waves per workgroup; a wave stages its coupled envs into a queue in LDS before its small solves, and 2 = shared (0 = default): any wave of the
+                                  workgroup claims them, the owner its own first, and a wave that has finished its step keeps serving the queue; 1 = owner only; 3 = always hand
+                                  off (another wave solves them: tests).  A/B switch only: the results are bit-identical under all three.  Other values: LCR_ERR_INVALID */
 } lcr_config;
 
 typedef enum lcr_solver { LCR_SOLVER_PGS = 0, LCR_SOLVER_NEWTON = 1 } lcr_solver;

@@ -27,8 +27,10 @@ for name in a.tasks:
         sim.step_device(bufs[i % 16].ptr)
         sim.sync()
         tot, solve, cpl, ch = (x.numpy()[::64].astype(np.float64) for x in (sim.max_sweeps, sim.active_mask, sim.active_count, sim.choice))
-        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0)))
-    tot, solve, cpl, ncpl, its, nslow = (np.stack([r[k] for r in rows]) for k in range(6))   # [step][wave]
+        # (one-cube Newton kernel, four-wave workgroups: lane 1 of active_count = cycles spent on other waves' patients, lane 2 = own patients other waves solved)
+        ac = sim.active_count.numpy().astype(np.float64)
+        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0), ac[1::64], ac[2::64]))
+    tot, solve, cpl, ncpl, its, nslow, helpc, handed = (np.stack([r[k] for r in rows]) for k in range(8))   # [step][wave]
     slow = tot.argmax(1)
     pick = lambda x: x[np.arange(len(slow)), slow].mean()
     print(f"{name:14s} n={a.n}: cycles per control step and wave, MEAN wave | SLOWEST wave of the step (mean over 20 steps)")
@@ -39,5 +41,8 @@ for name in a.tasks:
         print(f"   substeps in the coupled SIMT copy: {nslow.mean():.2f} | {pick(nslow):.2f}; waves with any: {100 * (nslow > 0).mean():.1f} %; cooperative solves per wave and step: {ncpl.mean():.2f} | {pick(ncpl):.2f}, most {ncpl.max():.0f}")
         srt = np.sort(tot.max(0))[::-1]
         print(f"   slowest waves (max over the steps), cycles: {' '.join(f'{v:.0f}' for v in srt[:6])};  p99 {np.percentile(tot, 99):.0f}  p90 {np.percentile(tot, 90):.0f}  p50 {np.percentile(tot, 50):.0f}")
+    if task != "stack" and task != "push_loop":
+        print(f"   cooperative cycles left on the owner's path (coupled solves above); cycles helping other waves {helpc.mean():10.0f} | {pick(helpc):10.0f};"
+              f" own patients handed off {handed.mean():.2f} | {pick(handed):.2f} of {ncpl.mean():.2f} | {pick(ncpl):.2f}")
     print(f"   Newton iterations executed by the wave: {its.mean():.1f} | {pick(its):.1f};  cycles per iteration (solves / iterations): {solve.sum() / max(its.sum(), 1):.0f}", flush=True)
     sim.close()
