@@ -27,14 +27,14 @@ def _newer(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# (source, object, extra flags): lcr_kernels.hip is compiled three times, LCR_PART selecting the step-kernel instantiations a unit emits
-# (0 one-cube kernels + dispatcher + small kernels, 2 / 3 the two StackTwoCubes variants) -- kernels of ~50-100 KB code each: 80 s in one
-# unit, ~30 s as units compiled concurrently; lcr_kernels_loop.hip is PushCubeLoop's unit
+# (source, object, extra flags): lcr_kernels.hip is compiled seven times, LCR_PART selecting the step-kernel instantiations a unit emits
+# (0 one-cube kernels + dispatcher + small kernels, 2 / 3 the two StackTwoCubes variants, 4 / 5 the Newton kernels, 6 / 7 PushCubeLoop's sweep /
+# Newton kernels) -- kernels of ~50-100 KB code each: 80 s in one unit, ~30 s as units compiled concurrently
 NO_POST_RA = ["-mllvm", "-enable-post-misched=0"]
 ITER_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 UNITS = [("lcr_capi.hip", "lcr_capi.o", []), ("lcr_render.hip", "lcr_render.o", []),
-         ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels_loop.hip", "lcr_kernels_loop.o", ["-DLCR_LOOP_PART=0"]),
-         ("lcr_kernels_loop.hip", "lcr_kernels_loop_newton.o", ["-DLCR_LOOP_PART=1"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
+         ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
+         ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),
          # the Newton kernels of the faithful preset: one cube / StackTwoCubes (eight cube<->cube slots).  Iterative-ILP scheduling, measured in round 6 against the default
          # (same box, tools/quick_times.py): ReachCube 65 536 envs 2.209 -> 2.082 ms, PushCube 3.499 -> 3.312, Stack 32 768 envs 7.06 -> 6.88, PushCubeLoop 6.60 -> 5.98;

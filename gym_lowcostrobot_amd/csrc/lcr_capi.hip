@@ -217,7 +217,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     if (cfg->cc_points == 8 && cfg->solver == LCR_SOLVER_PGS && cfg->diagnostics == 2) return fail(LCR_ERR_UNSUPPORTED, "cc_points = 8 runs on the two-wave kernels, diagnostics = 2 (per-wave cycles) on the one-wave kernels");
     if (cfg->cc_points == 8 && cfg->solver == LCR_SOLVER_PGS && cfg->step_kernel == 1) return fail(LCR_ERR_UNSUPPORTED, "cc_points = 8 is implemented by the two-wave kernels only (step_kernel = 1 pins the one-wave family)");
     if (cfg->step_kernel == 2 && cfg->pgs_iters < 0) return fail(LCR_ERR_UNSUPPORTED, "the converged solver mode (pgs_iters < 0) is implemented by the one-wave kernels only (step_kernel = 2 pins the two-wave family)");
-    if (cfg->step_kernel == 2 && cfg->task == LCR_TASK_PUSH_LOOP) return fail(LCR_ERR_UNSUPPORTED, "PushCubeLoop has the one-wave step kernel only (lcr_kernels_loop.hip); step_kernel = 2 pins the two-wave family");
+    if (cfg->step_kernel == 2 && cfg->task == LCR_TASK_PUSH_LOOP) return fail(LCR_ERR_UNSUPPORTED, "PushCubeLoop has the one-wave step kernel only (lcr_kernels.hip); step_kernel = 2 pins the two-wave family");
     if (cfg->step_kernel == 2 && cfg->diagnostics == 2) return fail(LCR_ERR_UNSUPPORTED, "diagnostics = 2 (per-wave cycles) reads back the one-wave kernels only (step_kernel = 2 pins the two-wave family)");
     if (cfg->solver != LCR_SOLVER_PGS && cfg->solver != LCR_SOLVER_NEWTON) return fail(LCR_ERR_INVALID, "solver must be LCR_SOLVER_PGS (0) or LCR_SOLVER_NEWTON (1)");
     if (cfg->finger_floor_condim != 0 && cfg->finger_floor_condim != 4 && cfg->finger_floor_condim != 6) return fail(LCR_ERR_INVALID, "finger_floor_condim must be 4 or 6");
@@ -370,7 +370,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
         // four one-cube tasks without rails (65 536 envs: ReachCube 0.257 against 0.285 ms, Push / Lift / PickPlace 0.308-0.312 against 0.333-0.336;
         // 32 768: 0.205-0.229 against 0.33) -- those tasks ALWAYS run them.  StackTwoCubes needs more than 256 registers per lane in its waves: up to
         // 32 768 envs (2 x 512 waves: one per SIMD) the two-wave kernels win (0.43 against 0.70 ms), above that one round of one-wave workgroups beats two
-        // rounds of two-wave ones (65 536: 0.78 against 0.82).  PushCubeLoop has one kernel (lcr_kernels_loop.hip, one wave per 64 envs).
+        // rounds of two-wave ones (65 536: 0.78 against 0.82).  PushCubeLoop has one kernel (lcr_kernels.hip, WALLS: one wave per 64 envs).
         // lcr_config.step_kernel pins a family (a Stack job cut into shards of <= 32 768 envs pins 2); LCR_STEP_KERNEL=single|coop1|coop2 overrides
         // (tests and profiling exercise every build).
         // WHICH BUILD of the two-wave family a shard runs does follow its size (one wave per SIMD while 2 x ceil(N / 64) waves fit the chip's SIMDs, else the

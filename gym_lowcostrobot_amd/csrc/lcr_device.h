@@ -85,11 +85,10 @@ struct LcrCam {
 
 // launchers implemented in lcr_kernels.hip / lcr_render.hip (plain C++ linkage, same shared object)
 int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
-// PushCubeLoop (lcr_kernels_loop.hip: one wave per 64 envs, row-wise solver)
-int lcr_launch_step_loop(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
 // the Newton kernels of the faithful preset (lcr_kernels.hip, unit LCR_PART = 4)
 int lcr_launch_step_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
 int lcr_launch_step_newton_stack(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);   // (unit LCR_PART = 5)
+int lcr_launch_step_loop_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);    // (PushCubeLoop: one wave per 64 envs, unit LCR_PART = 7)
 // two-cooperating-waves family (lcr_kernels2.hip); occ = waves per SIMD the variant is compiled for
 int lcr_launch_step2_one_cube(const LcrDev &P, const float *action_dev, int ee_mode, int occ, void *stream);
 int lcr_launch_step2_stack(const LcrDev &P, const float *action_dev, int ee_mode, int occ, void *stream);

@@ -9,7 +9,18 @@
 // [slot][row][k][lane] => bank-conflict free), the parked constants of the floor slots and, for Stack, the cube<->cube
 // contact records: 38-52 KiB per wave (LdsSize).  MFMA is not used: the largest contraction is 6x6.
 // Template variants of the step kernel: NC cubes (1|2), EE (ee-IK action mode), ADAPT (converged
-// solver mode), ROLL (six-row finger<->cube contacts), BIG (Stack shards of <= 3 waves per CU: every row in LDS).
+// solver mode), ROLL (six-row finger<->cube contacts), BIG (Stack shards of <= 3 waves per CU: every row in LDS),
+// NEWTON (the faithful preset), WALLS (PushCubeLoop, task 5: the four rails of push_cube_loop.xml:44-47, one cube).
+// WALLS keeps its own CONSTRAINT SOLVER in the sweep kernels: four Gauss-Seidel sweeps that update a contact's rows ONE AT A TIME
+// (each with its exact one-row step) and then scale the friction rows radially onto the elliptic cone, all rows in one sequence
+// (oracle: orc_params.cone = 0, jacobi = 0, the defaults of this task).  The other tasks take one
+// projected-gradient step per contact BLOCK in the second-order-cone variables with the rows in two concurrently swept groups
+// (soc_step); for PushCubeLoop's 15-mm cube of 50 g, whose torsional and rolling friction coefficients are 1.5 m
+// (push_cube_loop.xml:31), that step's group-wise step sizes are governed by the 1.5-m coefficients (scaled curvature mu^2 / I
+// four orders of magnitude above the tangential rows'), and four of its sweeps leave the normal forces of a pinched cube so far
+// from converged that cubes are thrown (oracle, 2048 envs x 200 random steps: fastest cube 14 m/s, 650 rad/s, centres 20 mm
+// under the floor; row-wise sweeps: 3.3 m/s, 57 rad/s, none under the floor; MuJoCo's optimum 3.1 m/s, 66 rad/s --
+// tools/loop_solver_study.py).  Its Newton kernel runs one wave per workgroup and solves its coupled envs itself.
 //
 // What is restated here (reference file:line, relative to /root/reference/gym_lowcostrobot/):
 //   apply_action joint mode   envs/reach_cube_env.py:248-273 (+ lift_cube_env.py:258-282 gripper)
@@ -20,6 +31,8 @@
 //   reward / success / done   envs/reach_cube_env.py:313-348, lift:322-346, push:330-361, pick_place:338-369,
 //                             stack_two_cubes_env.py:326-363; TimeLimit(50) from __init__.py:9-43
 //   reset                     envs/reach_cube_env.py:297-311, push:308-328, pick_place:316-336, stack:307-324
+//   PushCubeLoop              envs/push_cube_loop_env.py:224-275 apply_action, 277-279 mj_step, 319-383 step / reward /
+//                             goals, 299-317 reset; TimeLimit(50) from __init__.py:37-42; constants from push_cube_loop.xml
 #include "lcr_step_common.h"
 #include "lcr_newton.h"
 #include "lcr_newton_coop.h"
@@ -41,7 +54,7 @@ namespace {
 // 171 entries) do not set the register allocation of the substeps that do not need them.  CPL_FAST: every body is its own 6-dimensional SIMT problem; the envs of
 // the wave in which bodies touch (a finger or a gripper-body proxy on a cube, cube on cube) are solved one by one by the whole wave (lcr_newton_coop.h).  With more
 // than LcrDev::coop_max such envs the copy returns false -- the env state untouched -- and the substep is run by CPL_SLOW: the wave-uniform coupled SIMT solves of
-// round 5; it returns whether the wave still has that many (the caller goes back to the fast copy when not).  CPL_BOTH: one copy with both (PushCubeLoop).
+// round 5; it returns whether the wave still has that many (the caller goes back to the fast copy when not).  CPL_BOTH: the sweep kernels.
 constexpr int CPL_BOTH = 0, CPL_FAST = 1, CPL_SLOW = 2;
 
 // ---- the one-cube Newton kernel: four waves per workgroup (one per SIMD) and a queue of cooperative solves they share ----
@@ -60,7 +73,7 @@ static_assert(CQ_SLOT_F >= coop_stage_floats<1>() && CQ_SLOT_F >= 141 && 4 + CQ_
 static_assert(CQ_FLOATS * 4 <= 163840, "LDS of a CU");
 constexpr int CQ_FREE = 0, CQ_POSTED = 1, CQ_DONE = 2, CQ_LIVE = 3, CQ_OWNER = 4;
 [[maybe_unused]] constexpr int CQ_OWNER_ONLY = 0, CQ_SHARED = 1, CQ_HANDOFF = 2;   // LcrDev::coop_share
-template <int NC, bool NEWTON> constexpr bool cq_kernel() { return NEWTON && NC == 1; }
+template <int NC, bool NEWTON, bool WALLS> constexpr bool cq_kernel() { return NEWTON && NC == 1 && !WALLS; }   // (PushCubeLoop's Newton kernel: one wave, its own stage)
 
 struct CoopQueue {
     float *lds_all;   // wave w's g rows at lds_all + w * CQ_WAVE_FLOATS
@@ -131,11 +144,12 @@ DEV void cq_serve(const CoopQueue &Q, const NewtonParams &NP, int lane, unsigned
         __builtin_amdgcn_s_sleep(2);
     }
 }
-template <int NC, bool ADAPT, bool ROLL, bool BIG, bool NEWTON = false, int CPL = CPL_BOTH>
+template <int NC, bool ADAPT, bool ROLL, bool BIG, bool NEWTON = false, int CPL = CPL_BOTH, bool WALLS = false>
 DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float *lds, int lane, int env, f3 &lag_ee, f3 (&lag_cube)[NC], Warm<NC, ROLL ? 6 : 4> &W, Diag &DGtot, int sub_index) {
     static_assert(!NEWTON || (ROLL && !ADAPT && (NC == 1 || BIG)), "the Newton kernels carry six-row finger slots and keep every g row in LDS");
+    static_assert(!WALLS || (NC == 1 && !BIG), "PushCubeLoop has one cube");
     static_assert(CPL == CPL_BOTH || NEWTON, "two copies of the substep: the Newton kernels");
-    constexpr int NCC = NEWTON ? 8 : 4;   // cube<->cube manifold points (Stack): the Newton kernels carry eight slots, 4-7 in use with lcr_config.cc_points = 8
+    constexpr int NCC = (NEWTON && !WALLS) ? 8 : 4;   // cube<->cube manifold points (Stack): the Newton kernels carry eight slots, 4-7 in use with lcr_config.cc_points = 8
     constexpr int CCB = NEWTON ? NEWTON_G_ROWS : cc_base_rows<NC, BIG, ROLL>();   // first LDS row of the cube<->cube records
     constexpr int CCR = NEWTON ? CC_REC_NEWTON : CC_REC, CCRN = NEWTON ? CC_RN_NEWTON : 15;   // floats of a cube<->cube record, index of its Rn
     constexpr int NRW = ROLL ? 6 : 4;   // rows an arm slot may have
@@ -320,7 +334,12 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
             T.aref[2] = B_DEF * vp.x;       // t2 = -x
             T.aref[3] = -B_DEF * cww[c].z;  // torsion about n
             // (an inactive slot gets inv = 0: with f = 0 its row updates then come out as exactly zero in the sweeps, no per-sweep selects)
-            {   // k[] of the block step (lcr_step_common.h soc_step): Ln = 2 (A + R)_nn, Lt = 2 (mu^2 ((A + R)_11 + (A + R)_22) + mu_tors^2 (A + R)_33)
+            if constexpr (WALLS) {   // inverse diagonals of the row-wise sweeps
+                T.inv[0] = T.act ? rcp(minv + iinv * (T.r.x * T.r.x + T.r.y * T.r.y) + Rn) : 0.f;
+                T.inv[1] = T.act ? rcp(minv + iinv * (T.r.z * T.r.z + T.r.x * T.r.x) + Rf) : 0.f;
+                T.inv[2] = T.act ? rcp(minv + iinv * (T.r.z * T.r.z + T.r.y * T.r.y) + Rf) : 0.f;
+                T.inv[3] = T.act ? rcp(iinv + Rt) : 0.f;
+            } else {   // k[] of the block step (lcr_step_common.h soc_step): Ln = 2 (A + R)_nn, Lt = 2 (mu^2 ((A + R)_11 + (A + R)_22) + mu_tors^2 (A + R)_33)
                 const float KF = 2.f;   // (two groups, see soc_step)
                 const float Ln = KF * (minv + iinv * (T.r.x * T.r.x + T.r.y * T.r.y) + Rn);
                 const float a12 = 2.f * minv + iinv * (2.f * T.r.z * T.r.z + T.r.x * T.r.x + T.r.y * T.r.y) + 2.f * Rf;
@@ -354,7 +373,7 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
 #pragma unroll
     for (int s = 0; s < NCC; s++) cc_act[s] = false;
     bool cc_any = false;
-    const bool real_lane = (int)(blockIdx.x * (cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64) + (cq_kernel<NC, NEWTON>() ? (int)threadIdx.x : lane)) < P.n;   // (the tail lanes of a ragged batch shadow the last env and store nothing: they are nobody's patient)
+    const bool real_lane = (int)(blockIdx.x * (cq_kernel<NC, NEWTON, WALLS>() ? 64 * CQ_WAVES : 64) + (cq_kernel<NC, NEWTON, WALLS>() ? (int)threadIdx.x : lane)) < P.n;   // (the tail lanes of a ragged batch shadow the last env and store nothing: they are nobody's patient)
     int cc_count = 0;       // (Stack) cube<->cube points of this lane
     bool coupled = false;   // (NEWTON) bodies of this lane's env touch -- its arm a cube, cube on cube --: they are ONE problem
     f3 ccn = mk(0.f, 0.f, 1.f), cct1 = mk(0.f, 1.f, 0.f), cct2 = mk(-1.f, 0.f, 0.f);
@@ -522,6 +541,103 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
         }
     }
 
+    // ---- collision: PushCubeLoop rails.  The four wall boxes act as their inner faces (vertical half-spaces below the wall
+    //      top).  The pen is wider than the cube in both directions, so at most one x rail and one y rail can be touched:
+    //      slots 0,1 belong to the x pair (left rail if any vertex is beyond it, else right), slots 2,3 to the y pair
+    //      (bottom if touched, else top); each pair keeps its two deepest vertices.  With axis-aligned normals the rows
+    //      have the closed form of the floor rows; the y pair is the x pair under the cyclic relabelling x->y->z->x. ----
+    FloorSlot WS[4];   // r holds the contact point in the pair's (cyclically permuted) coordinates
+    float wsg[2] = {1.f, 1.f};   // sign of the pair's normal along its axis
+    bool wall_any = false;
+    if constexpr (WALLS) {
+#pragma unroll
+        for (int s = 0; s < 4; s++) { WS[s].act = false; WS[s].r = mk(0.f, 0.f, 0.f); WS[s].Rn = 1.f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) { WS[s].f[k] = 0.f; WS[s].aref[k] = 0.f; WS[s].inv[k] = 0.f; } }
+        f3 vw[8];
+        float worst = 1.f;
+        bool lo_x = false, lo_y = false;
+        const bool inpen = cube_in_pen(S.cp[0]);   // (a cube outside the rails' outer rectangle touches no rail)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const float sx = (i & 1) ? CH : -CH, sy = (i & 2) ? CH : -CH, sz = (i & 4) ? CH : -CH;
+            vw[i] = axpy(sx, CR[0].X, axpy(sy, CR[0].Y, sz * CR[0].Z));   // relative to the cube centre
+            const f3 p = vw[i] + S.cp[0];
+            const bool low = p.z < WALL_TOP;
+            const float dmin = fminf(fminf(p.x + WALL_X, WALL_X - p.x), fminf(p.y - WALL_Y0, WALL_Y1 - p.y));
+            worst = fminf(worst, (low && inpen) ? dmin : 1.f);
+            lo_x = lo_x || (low && inpen && p.x + WALL_X < 0.f);
+            lo_y = lo_y || (low && inpen && p.y - WALL_Y0 < 0.f);
+        }
+        wall_any = __any(worst < 0.f) != 0;
+        if (wall_any) {
+            wsg[0] = lo_x ? 1.f : -1.f;
+            wsg[1] = lo_y ? 1.f : -1.f;
+#pragma unroll
+            for (int pr = 0; pr < 2; pr++) {
+                const float sg = wsg[pr];
+                const float off = pr == 0 ? WALL_X : (sg > 0.f ? -WALL_Y0 : WALL_Y1);
+                // the two deepest vertices beyond this face (ties: lower vertex index first)
+                float d1 = 0.f, d2 = 0.f;
+                bool h1 = false, h2 = false;
+                f3 r1 = mk(0.f, 0.f, 0.f), r2 = mk(0.f, 0.f, 0.f);
+                int i1 = 0, i2 = 0;   // vertex indices of the two (diagnostics only)
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const f3 p = vw[i] + S.cp[0];
+                    const float dist = fmaf(sg, pr == 0 ? p.x : p.y, off);
+                    const bool pen = dist < 0.f && p.z < WALL_TOP && inpen;
+                    const bool first = pen && (!h1 || dist < d1);
+                    const bool second = pen && !first && (!h2 || dist < d2);
+                    if (P.diag) { i2 = first ? i1 : (second ? i : i2); i1 = first ? i : i1; }
+                    d2 = first ? d1 : (second ? dist : d2);
+                    r2 = first ? r1 : (second ? vw[i] : r2);
+                    h2 = first ? h1 : (second ? true : h2);
+                    d1 = first ? dist : d1;
+                    r1 = first ? vw[i] : r1;
+                    h1 = h1 || first;
+                }
+                // pair coordinates (a, b, c) = (x, y, z) for the x pair, (y, z, x) for the y pair
+                const f3 v = pr == 0 ? S.cv[0] : mk(S.cv[0].y, S.cv[0].z, S.cv[0].x);
+                const f3 w = pr == 0 ? cww[0] : mk(cww[0].y, cww[0].z, cww[0].x);
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    FloorSlot &T = WS[2 * pr + c];
+                    const float dist = fmaxf(c == 0 ? d1 : d2, -RAIL_CLAMP);   // (round 5: a rail reports at most RAIL_CLAMP of penetration, lcr_step_common.h)
+                    const f3 rw = c == 0 ? r1 : r2;
+                    T.act = c == 0 ? h1 : h2;
+                    if (P.diag) diag_choice(DG, T.act, 8 + 2 * pr + c, (c == 0 ? i1 : i2) + 8 * (2 * pr + (sg > 0.f ? 0 : 1)));
+                    f3 r = pr == 0 ? rw : mk(rw.y, rw.z, rw.x);
+                    r.x = fmaf(-0.5f * dist, sg, r.x);   // contact point midway between vertex and face
+                    T.r = r;
+                    float imp = impedance(dist, D0_DEF, DW_DEF, 1.0f / W_DEF);
+                    float Rn = fmaxf((1.f - imp) * rcp(imp) * minv, 1e-15f);
+                    float Rf = Rn * P.inv_impratio;
+                    float Rt = Rf * P.rt_cube;
+                    T.Rn = Rn;
+                    const f3 vp = v + cross(w, r);   // velocity of the contact point; n = (sg,0,0), t1 = (0,1,0), t2 = (0,0,sg)
+                    T.aref[0] = -B_DEF * sg * vp.x - K_DEF * imp * dist;
+                    T.aref[1] = -B_DEF * vp.y;
+                    T.aref[2] = -B_DEF * sg * vp.z;
+                    T.aref[3] = -B_DEF * sg * w.x;
+                    T.inv[0] = T.act ? rcp(minv + iinv * (r.y * r.y + r.z * r.z) + Rn) : 0.f;
+                    T.inv[1] = T.act ? rcp(minv + iinv * (r.x * r.x + r.z * r.z) + Rf) : 0.f;
+                    T.inv[2] = T.act ? rcp(minv + iinv * (r.x * r.x + r.y * r.y) + Rf) : 0.f;
+                    T.inv[3] = T.act ? rcp(iinv + Rt) : 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) T.f[k] = T.act ? W.wall[2 * pr + c][k] : 0.f;   // warm start
+                    // a += M^-1 J^T f in pair coordinates
+                    const float la = minv * sg * T.f[0], lb = minv * T.f[1], lc = minv * sg * T.f[2];
+                    const float aa = iinv * (-r.z * T.f[1] + sg * r.y * T.f[2] + sg * T.f[3]);
+                    const float ab = iinv * sg * (r.z * T.f[0] - r.x * T.f[2]);
+                    const float ac = iinv * (-sg * r.y * T.f[0] + r.x * T.f[1]);
+                    if (pr == 0) { ca[0] = ca[0] + mk(la, lb, lc); cal[0] = cal[0] + mk(aa, ab, ac); }
+                    else { ca[0] = ca[0] + mk(lc, la, lb); cal[0] = cal[0] + mk(ac, aa, ab); }
+                }
+            }
+        }
+    }
+
     // ---- collision: arm-coupled contact slots (NAS): finger spheres vs cube / floor, arm-link proxies (D3); rows g = L^-1 J^T
     //      go to LDS.  Every slot is skipped wave-uniformly when no lane of the wave touches. ----
     ArmSlot<NRW> AS[NAS];
@@ -529,6 +645,8 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
     bool link_on_cube = false;       // slot 4: this lane's contact is against a cube (else the floor)
     int link_nj = 3;             // slot 4: number of joints that move the contact point (proxy on link_3: 3 ... link_6: 6)
     int link_bi = 0;             // slot 4: which proxy
+    f3 link_n = mk(0.f, 0.f, 1.f);   // slot 4 on the world: normal and code of the surface the proxy meets (floor, or a rail's top / side face: D7, world_surface)
+    int link_code = 0;
     int slot_cube[3] = {0, 0, 0};  // which cube the cube slots 0, 1 and 4 refer to (Stack)
     {
     const f3 sph[2] = {local_point(F, 4, SPH0x, SPH0y, SPH0z), local_point(F, 5, SPH1x, SPH1y, SPH1z)};
@@ -576,8 +694,13 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
         } else if (s < 4) {
             if constexpr (NEWTON) {
                 const int L = sp == 0 ? 4 : 5;
-                const PadFloorHit hit = pad_floor<false>(PadBox{padc[sp], padh[sp].x * F.X[L], padh[sp].y * F.Y[L], padh[sp].z * F.Z[L]});
-                dist = hit.dist; pos = hit.pos; sel = hit.code;
+                const PadFloorHit hit = pad_floor<WALLS>(PadBox{padc[sp], padh[sp].x * F.X[L], padh[sp].y * F.Y[L], padh[sp].z * F.Z[L]});
+                dist = hit.dist; pos = hit.pos; sel = hit.code; n = hit.n;
+            } else if constexpr (WALLS) {   // the floor, or a rail's top or SIDE face (world_surface)
+                const WorldHit w = world_surface<WALLS>(sph[sp], srad[sp]);
+                dist = -w.depth; n = w.n;
+                pos = axpy(-(srad[sp] + 0.5f * dist), w.n, sph[sp]);
+                sel = w.code;   // (which surface: part of the decision signature)
             } else {
                 dist = sph[sp].z - srad[sp];
                 pos = mk(sph[sp].x, sph[sp].y, 0.5f * dist);
@@ -604,8 +727,14 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
             for (int i = 0; i < 5; i++) {
                 const int L = plink[i];
                 const float cz = fmaf(px[i], F.X[L].z, fmaf(py[i], F.Y[L].z, fmaf(pz[i], F.Z[L].z, F.p[L].z)));
-                const float df = cz - pr[i];
-                if (df < bestd) { bestd = df; bi = i; oncube = false; }
+                float df = cz - pr[i];
+                f3 wn = mk(0.f, 0.f, 1.f);
+                int wcode = 0;
+                if constexpr (WALLS) {   // (D7) the floor, or a rail's top or side face
+                    const WorldHit w = world_surface<WALLS>(local_point(F, L, px[i], py[i], pz[i]), pr[i]);
+                    df = -w.depth; wn = w.n; wcode = w.code;
+                }
+                if (df < bestd) { bestd = df; bi = i; oncube = false; link_n = wn; link_code = wcode; }
                 if (i >= 3 && wave_near) {
                     const f3 ci = local_point(F, L, px[i], py[i], pz[i]);
 #pragma unroll
@@ -616,7 +745,7 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 }
             }
             link_bi = bi;
-            if (!oncube) { n = mk(0.f, 0.f, 1.f); sel = 0; }
+            if (!oncube) { n = link_n; sel = link_code; }
             sel += 64 * (bi + 1);
             dist = bestd;
             link_on_cube = oncube;
@@ -649,17 +778,30 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 // five computed points would be turned into a scratch array by the compiler)
                 const float qx[5] = {LPX0x, LPX1x, LPX2x, LPX3x, LPX4x}, qy[5] = {LPX0y, LPX1y, LPX2y, LPX3y, LPX4y}, qz[5] = {LPX0z, LPX1z, LPX2z, LPX3z, LPX4z};
                 const int ql[5] = {2, 2, 3, 4, 5};
-                f2v cb = {0.f, 0.f};
+                if constexpr (WALLS) {
+                    const float qr[5] = {LPX0r, LPX1r, LPX2r, LPX3r, LPX4r};
+                    f3 cb = mk(0.f, 0.f, 0.f);
+                    float rb = 0.f;
 #pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    const float m = link_bi == i ? 1.f : 0.f;
-                    const int L = ql[i];
-                    const f2v ci = F.p[L].xy + f2v{qx[i], qx[i]} * F.X[L].xy + f2v{qy[i], qy[i]} * F.Y[L].xy + f2v{qz[i], qz[i]} * F.Z[L].xy;
-                    cb = f2v{m, m} * ci + cb;
+                    for (int i = 0; i < 5; i++) {
+                        const float m = link_bi == i ? 1.f : 0.f;
+                        cb = axpy(m, local_point(F, ql[i], qx[i], qy[i], qz[i]), cb);
+                        rb = fmaf(m, qr[i], rb);
+                    }
+                    if (!oncube) pos = axpy(-(rb + 0.5f * dist), n, cb);   // midway between the proxy's surface and the world surface it is inside
+                } else {
+                    f2v cb = {0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 5; i++) {
+                        const float m = link_bi == i ? 1.f : 0.f;
+                        const int L = ql[i];
+                        const f2v ci = F.p[L].xy + f2v{qx[i], qx[i]} * F.X[L].xy + f2v{qy[i], qy[i]} * F.Y[L].xy + f2v{qz[i], qz[i]} * F.Z[L].xy;
+                        cb = f2v{m, m} * ci + cb;
+                    }
+                    if (!oncube) pos = mk(cb.x, cb.y, 0.5f * dist);
                 }
-                if (!oncube) pos = mk(cb.x, cb.y, 0.5f * dist);
             }
-            if (may_cube) make_frame(n, T.t1, T.t2);   // (for n = +z this is the floor frame t1 = +y, t2 = -x)
+            if (may_cube || WALLS) make_frame(n, T.t1, T.t2);   // (for n = +z this is the floor frame t1 = +y, t2 = -x; PushCubeLoop: a rail's side face has a horizontal normal)
             // joints that move the contact point: the finger spheres sit on link_5 / link_6, the proxies on link_3..link_6
             auto joint_on = [&](int j) -> bool {
                 if (s < 4) return j < (sp == 0 ? 5 : 6);
@@ -772,7 +914,9 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 T.aref[r] = -Bc * vel - (r == 0 ? Kc * imp * dist : 0.f);
                 // warm start: previous substep's force of this slot (zero if it was inactive), applied to the accelerations
                 const bool row_on = T.act && (s != 4 || r < 3 || oncube);   // a link proxy on the floor has no torsion row (condim 3)
-                {
+                if constexpr (WALLS) {
+                    T.inv[r] = row_on ? rcp(gg + diagc + Rr) : 0.f;              // (a row that is off: f = 0 and inv = 0 -> its updates are exactly 0)
+                } else {
                     const float arr = gg + diagc + Rr;
                     const float m2r = r == 0 ? 1.f : (r < 3 ? m2_tan : (r == 3 ? m2_tors : P.mu_fcr2));
                     const float KF = 2.f;
@@ -798,7 +942,7 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
 #pragma unroll
                 for (int j = 0; j < 6; j++) y[j] = fmaf(Bb[0][j], tau.x, fmaf(Bb[1][j], tau.y, fmaf(Bb[2][j], tau.z, y[j])));
             }
-            {   // k[] of soc_step: iLn, mu_tan^2 iLt, w, mu_tors^2 iLt (, mu_roll^2 iLt)
+            if constexpr (!WALLS) {   // k[] of soc_step: iLn, mu_tan^2 iLt, w, mu_tors^2 iLt (, mu_roll^2 iLt)
                 const float iLn = T.act ? rcp(Ln) : 0.f, iLt = T.act ? rcp(Lt) : 0.f, iLs = iLt;
                 T.inv[0] = iLn; T.inv[1] = m2_tan * iLt; T.inv[2] = Ln * rcp(Ln + Lt); T.inv[3] = (s != 4 || oncube) ? m2_tors * iLs : 0.f;   // (a link proxy on the floor has no torsion row: condim 3)
                 if constexpr (ROLL) { T.inv[4] = P.mu_fcr2 * iLs; T.inv[5] = 0.f; }
@@ -847,9 +991,7 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
         const int row0[NAS] = {arm_row0_of<ROLL, NC, BIG, NEWTON>(0), arm_row0_of<ROLL, NC, BIG, NEWTON>(1), arm_row0_of<ROLL, NC, BIG, NEWTON>(2),
                                arm_row0_of<ROLL, NC, BIG, NEWTON>(3), arm_row0_of<ROLL, NC, BIG, NEWTON>(4)};
         const NewtonParams NP = newton_params(P);
-        FloorSlot no_walls[4];
-        const float no_wsg[2] = {1.f, 1.f};
-        NewtonCtx<NC, NRW, false, NCC> C{NP, lds, lane, row0, AS, slot_any, link_on_cube, slot_cube, FS, no_walls, no_wsg, false,
+        NewtonCtx<NC, NRW, WALLS, NCC> C{NP, lds, lane, row0, AS, slot_any, link_on_cube, slot_cube, FS, WS, wsg, wall_any,
                                          ccl, cc_act, cc_any, ccn, cct1, cct2, S.cp, lim_act, lim_wave, S.q, S.qd, CL, flim, y0s};
         const long long tn0 = P.diag == 2 ? clock64() : 0;   // (profiling aid: cycles of the solves, of the coupled ones, iterations -- tools/newton_phases.py)
         bool prof_coupled = false;
@@ -860,13 +1002,27 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
             prof_coupled = arm_on_cube;
             const unsigned long long cmask = __ballot(coupled);
             coupled_any = __popcll(cmask) > P.coop_max;   // (CPL_SLOW: stay in this copy while more lanes are coupled than the cooperative solve takes)
-            if constexpr (CPL == CPL_SLOW) sweeps_done = newton_solve<NC, NRW, false, NCC, 3>(C, y, ca, cal);   // (uncoupled lanes: the same optimum, block-diagonal Hessian)
-            else if (CPL == CPL_BOTH && arm_on_cube) sweeps_done = newton_solve<NC, NRW, false, NCC, 3>(C, y, ca, cal);
+            if constexpr (CPL == CPL_SLOW) sweeps_done = newton_solve<NC, NRW, WALLS, NCC, 3>(C, y, ca, cal);   // (uncoupled lanes: the same optimum, block-diagonal Hessian)
+            else if (CPL == CPL_BOTH && arm_on_cube) sweeps_done = newton_solve<NC, NRW, WALLS, NCC, 3>(C, y, ca, cal);
             else {
                 // the lanes whose arm touches their cube sit out the two small solves; they are staged into the workgroup's queue first and solved four per pass by
-                // whichever wave claims them (CoopQueue above)
+                // whichever wave claims them (CoopQueue above) -- PushCubeLoop's one-wave workgroup solves them itself after the small solves
                 C.enable = (CPL == CPL_BOTH || !coupled) ? 7 : 0;
-                if constexpr (CPL == CPL_FAST) {
+                if constexpr (CPL == CPL_FAST && WALLS) {
+                    const int ia = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal);
+                    const int ic = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal);
+                    sweeps_done = max(ia, ic);
+                    float *stage = lds + NEWTON_G_ROWS * LDS_ROW;
+                    const long long tc0 = P.diag == 2 ? clock64() : 0;
+                    // four patients per pass, one per 16-lane row: 13 contact blocks + the six joint limits in one lane (coop_solve_rows; one patient at a time with
+                    // all 64 lanes, 19 blocks, was slower)
+                    for (unsigned long long m = cmask; m != 0ull;) {
+                        unsigned long long pm = 0ull;
+                        for (int k = 0; k < 4 && m != 0ull; k++) { pm |= m & (0ull - m); m &= m - 1ull; }
+                        coop_solve_rows<NC, NRW, NCC, WALLS>(C, stage, lane, pm, 0ull, y, ca, cal, sweeps_done);
+                    }
+                    if (P.diag == 2) { prof_coop = (unsigned)(clock64() - tc0); prof_patients = __popcll(cmask); }
+                } else if constexpr (CPL == CPL_FAST) {
                     const int wv = (int)(threadIdx.x >> 6);
                     float *lds_all = lds - wv * CQ_WAVE_FLOATS;
                     const CoopQueue Q{lds_all, lds_all + CQ_WAVES * CQ_WAVE_FLOATS, reinterpret_cast<int *>(lds_all + CQ_WAVES * CQ_WAVE_FLOATS + CQ_SLOTS * CQ_SLOT_F), wv, P.coop_share};
@@ -893,8 +1049,8 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                     };
                     post();
                     if (P.diag == 2) tsmall = clock64();
-                    const int ia = newton_solve<NC, NRW, false, NCC, 1>(C, y, ca, cal);
-                    const int ic = newton_solve<NC, NRW, false, NCC, 2>(C, y, ca, cal);
+                    const int ia = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal);
+                    const int ic = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal);
                     sweeps_done = max(ia, ic);
                     if (P.diag == 2) tsmall = clock64() - tsmall;
                     int its = 0;
@@ -936,8 +1092,8 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                     C.wave_its += its;
                     if (P.diag == 2) prof_coop = (unsigned)(clock64() - tc0 - tsmall);
                 } else {
-                    const int ia = newton_solve<NC, NRW, false, NCC, 1>(C, y, ca, cal);
-                    const int ic = newton_solve<NC, NRW, false, NCC, 2>(C, y, ca, cal);
+                    const int ia = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal);
+                    const int ic = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal);
                     sweeps_done = max(ia, ic);
                 }
             }
@@ -958,28 +1114,21 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 // random actions --, all three bodies (18 unknowns) otherwise
                 const bool pair0 = on0 && !on1 && !(cc_any && cc_count > 0), pair1 = on1 && !on0 && !(cc_any && cc_count > 0);
                 C.enable = !coupled ? 7 : (pair0 ? 4 : (pair1 ? 2 : 0));
-                i1 = newton_solve<NC, NRW, false, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, false, NCC, 2>(C, y, ca, cal);
-                i3 = newton_solve<NC, NRW, false, NCC, 4>(C, y, ca, cal);
+                i1 = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal);
+                i3 = newton_solve<NC, NRW, WALLS, NCC, 4>(C, y, ca, cal);
                 float *stage = lds + NEWTON_G_ROWS * LDS_ROW + 8 * CCR * 64;
                 const long long tc0 = P.diag == 2 ? clock64() : 0;
                 prof_patients = __popcll(cmask);
                 const unsigned long long m0 = __ballot(pair0), m1 = __ballot(pair1);
-#ifdef LCR_STACK_ONE_PER_PASS
-                // (A/B: one patient at a time with all 64 lanes -- Stack, 32 768 envs: 6.81 ms against 6.03 with four per pass)
-                for (unsigned long long m = m0 | m1; m != 0ull; m &= m - 1ull) {
-                    const int L = __builtin_ctzll(m);
-                    const int ip = coop_solve<NC, NRW, NCC, 1>(C, stage, lane, L, y, ca, cal, (int)(m1 >> L & 1ull));
-                    i1 = lane == L ? max(ip, i1) : i1;
-                }
-#else
-                for (unsigned long long m = m0 | m1; m != 0ull;) {   // arm + one cube: four patients per pass, one per 16-lane row (coop_solve_rows)
+                // arm + one cube: four patients per pass, one per 16-lane row (coop_solve_rows; one patient at a time with all 64 lanes -- Stack, 32 768 envs: 6.81 ms
+                // against 6.03)
+                for (unsigned long long m = m0 | m1; m != 0ull;) {
                     unsigned long long pm = 0ull;
                     for (int k = 0; k < 4 && m != 0ull; k++) { pm |= m & (0ull - m); m &= m - 1ull; }
                     int ip = 0;
                     coop_solve_rows<NC, NRW, NCC>(C, stage, lane, pm, m1, y, ca, cal, ip);
                     i1 = max(ip, i1);
                 }
-#endif
                 for (unsigned long long m = cmask & ~(m0 | m1); m != 0ull; m &= m - 1ull) {   // all three bodies: one patient at a time
                     const int L = __builtin_ctzll(m);
                     const int ip = coop_solve<NC, NRW, NCC, 2>(C, stage, lane, L, y, ca, cal);
@@ -987,13 +1136,13 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 }
                 if (P.diag == 2) prof_coop = (unsigned)(clock64() - tc0);
             } else
-            if ((eA0 && eA1) || (e01 && (eA0 || eA1))) i1 = newton_solve<NC, NRW, false, NCC, 7>(C, y, ca, cal);
-            else if (eA0) { i1 = newton_solve<NC, NRW, false, NCC, 3>(C, y, ca, cal); i2 = newton_solve<NC, NRW, false, NCC, 4>(C, y, ca, cal); }
-            else if (eA1) { i1 = newton_solve<NC, NRW, false, NCC, 5>(C, y, ca, cal); i2 = newton_solve<NC, NRW, false, NCC, 2>(C, y, ca, cal); }
-            else if (e01) { i1 = newton_solve<NC, NRW, false, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, false, NCC, 6>(C, y, ca, cal); }
+            if ((eA0 && eA1) || (e01 && (eA0 || eA1))) i1 = newton_solve<NC, NRW, WALLS, NCC, 7>(C, y, ca, cal);
+            else if (eA0) { i1 = newton_solve<NC, NRW, WALLS, NCC, 3>(C, y, ca, cal); i2 = newton_solve<NC, NRW, WALLS, NCC, 4>(C, y, ca, cal); }
+            else if (eA1) { i1 = newton_solve<NC, NRW, WALLS, NCC, 5>(C, y, ca, cal); i2 = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal); }
+            else if (e01) { i1 = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, WALLS, NCC, 6>(C, y, ca, cal); }
             else {
-                i1 = newton_solve<NC, NRW, false, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, false, NCC, 2>(C, y, ca, cal);
-                i3 = newton_solve<NC, NRW, false, NCC, 4>(C, y, ca, cal);
+                i1 = newton_solve<NC, NRW, WALLS, NCC, 1>(C, y, ca, cal); i2 = newton_solve<NC, NRW, WALLS, NCC, 2>(C, y, ca, cal);
+                i3 = newton_solve<NC, NRW, WALLS, NCC, 4>(C, y, ca, cal);
             }
             sweeps_done = max(i1, max(i2, i3));
             prof_coupled = eA0 || eA1 || e01;
@@ -1162,10 +1311,12 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
             }
         }
         // group A: (two cubes: finger<->cube,) finger<->floor, arm-link proxies (after the joint limits above)
-        if constexpr (NC == 2) { arm_slot(std::integral_constant<int, 0>{}); arm_slot(std::integral_constant<int, 1>{}); }
-        arm_slot(std::integral_constant<int, 2>{});
-        arm_slot(std::integral_constant<int, 3>{});
-        arm_slot(std::integral_constant<int, 4>{});
+        if constexpr (!WALLS) {
+            if constexpr (NC == 2) { arm_slot(std::integral_constant<int, 0>{}); arm_slot(std::integral_constant<int, 1>{}); }
+            arm_slot(std::integral_constant<int, 2>{});
+            arm_slot(std::integral_constant<int, 3>{});
+            arm_slot(std::integral_constant<int, 4>{});
+        }
         // floor <-> cube
 #pragma unroll
         for (int c = 0; c < NC; c++) {
@@ -1188,12 +1339,30 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 const float u1 = ca[c].y - r.z * cal[c].x + r.x * cal[c].z - aref1 + Rf * T.f[1];
                 const float u2 = -ca[c].x - r.z * cal[c].y + r.y * cal[c].z - aref2 + Rf * T.f[2];
                 const float u3 = cal[c].z - aref3 + Rt * T.f[3];
-                // one projected-gradient step of the whole block (soc_step): the four gradient rows above are taken from the same accelerations
-                const float uu[4] = {u0, u1, u2, u3}, kk[4] = {inv0, inv1, inv2, inv3};
-                float nf[4];
-                soc_step<4>(T.f, uu, kk, P.inv_mu_c2, P.inv_mu_ct2, 0.f, 4, nf);
-                const float d0 = nf[0] - T.f[0], d1 = nf[1] - T.f[1], d2 = nf[2] - T.f[2], d3 = nf[3] - T.f[3];   // (inactive slot: f = 0, k = 0 -> every delta is 0)
-                T.f[0] = nf[0]; T.f[1] = nf[1]; T.f[2] = nf[2]; T.f[3] = nf[3];
+                float d0, d1, d2, d3;   // (inactive slot: f = 0, k = inv = 0 -> every delta is 0)
+                if constexpr (WALLS) {
+                    // the four Gauss-Seidel row updates in block form (same arithmetic as row by row): the residuals u_r are independent of each other, the coupling
+                    // inside the contact is the 4x4 block B = J M^-1 J^T, so the dependent chain is 4 short steps instead of 4 full row sweeps
+                    const float B01 = -iinv * r.y * r.z, B02 = iinv * r.x * r.z, B12 = iinv * r.x * r.y, B13 = iinv * r.x, B23 = iinv * r.y;
+                    const float nf = fmaxf(T.f[0] - u0 * inv0, 0.f);
+                    d0 = nf - T.f[0];
+                    const float d1a = -(u1 + B01 * d0) * inv1;
+                    const float d2a = -(u2 + B02 * d0 + B12 * d1a) * inv2;
+                    const float d3a = -(u3 + B13 * d1a + B23 * d2a) * inv3;
+                    // elliptic cone: radial projection of the friction part
+                    const float fn = T.f[0] + d0;
+                    const float g1 = T.f[1] + d1a, g2 = T.f[2] + d2a, g3 = T.f[3] + d3a;
+                    const float s2 = (g1 * g1 + g2 * g2) * P.inv_mu_c2 + g3 * g3 * P.inv_mu_ct2;
+                    const float sc = clampf(fn * rsq(fmaxf(s2, 1e-30f)), 0.f, 1.f);
+                    d1 = g1 * sc - T.f[1]; d2 = g2 * sc - T.f[2]; d3 = g3 * sc - T.f[3];
+                    T.f[0] = fn; T.f[1] += d1; T.f[2] += d2; T.f[3] += d3;
+                } else {   // one projected-gradient step of the whole block (soc_step): the four gradient rows above are taken from the same accelerations
+                    const float uu[4] = {u0, u1, u2, u3}, kk[4] = {inv0, inv1, inv2, inv3};
+                    float nf[4];
+                    soc_step<4>(T.f, uu, kk, P.inv_mu_c2, P.inv_mu_ct2, 0.f, 4, nf);
+                    d0 = nf[0] - T.f[0]; d1 = nf[1] - T.f[1]; d2 = nf[2] - T.f[2]; d3 = nf[3] - T.f[3];
+                    T.f[0] = nf[0]; T.f[1] = nf[1]; T.f[2] = nf[2]; T.f[3] = nf[3];
+                }
                 track(d0, d1, d2, d3, T.f[0], T.f[1], T.f[2], T.f[3]);   // (converged mode: net change of the sweep, after the cone projection)
                 // a += M^-1 J^T delta
                 ca[c].z = fmaf(minv, d0, ca[c].z);
@@ -1244,10 +1413,190 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
                 }
             }
         }
-        // group B, second part: finger<->cube
-        if constexpr (NC == 1) { arm_slot(std::integral_constant<int, 0>{}); arm_slot(std::integral_constant<int, 1>{}); }
+        if constexpr (WALLS) {
+            // rails (PushCubeLoop): block form of the four rows of each contact, as for the floor
+            if (wall_any) {
 #pragma unroll
-        for (int c = 0; c < NC; c++) { ca[c] = ca[c] + dcaA[c]; cal[c] = cal[c] + dcalA[c]; }   // group A's share of the cube accelerations (slot 4)
+                for (int s = 0; s < 4; s++) {
+                    FloorSlot &T = WS[s];
+                    const int pr = s >> 1;
+                    const float sg = wsg[pr];
+                    const f3 r = T.r;
+                    const float Rf = T.Rn * P.inv_impratio, Rt = Rf * P.rt_cube;
+                    const f3 a = pr == 0 ? ca[0] : mk(ca[0].y, ca[0].z, ca[0].x);
+                    const f3 w = pr == 0 ? cal[0] : mk(cal[0].y, cal[0].z, cal[0].x);
+                    const float u0 = sg * (a.x + r.z * w.y - r.y * w.z) - T.aref[0] + T.Rn * T.f[0];
+                    const float u1 = a.y - r.z * w.x + r.x * w.z - T.aref[1] + Rf * T.f[1];
+                    const float u2 = sg * (a.z + r.y * w.x - r.x * w.y) - T.aref[2] + Rf * T.f[2];
+                    const float u3 = sg * w.x - T.aref[3] + Rt * T.f[3];
+                    const float B01 = -sg * iinv * r.x * r.y, B02 = -iinv * r.x * r.z, B12 = -sg * iinv * r.y * r.z;
+                    const float B13 = -sg * iinv * r.z, B23 = iinv * r.y;
+                    const float nf = fmaxf(T.f[0] - u0 * T.inv[0], 0.f);
+                    const float d0 = nf - T.f[0];
+                    const float d1a = -(u1 + B01 * d0) * T.inv[1];
+                    const float d2a = -(u2 + B02 * d0 + B12 * d1a) * T.inv[2];
+                    const float d3a = -(u3 + B13 * d1a + B23 * d2a) * T.inv[3];
+                    // elliptic cone: radial projection of the friction part
+                    const float fn = T.f[0] + d0;
+                    const float g1 = T.f[1] + d1a, g2 = T.f[2] + d2a, g3 = T.f[3] + d3a;
+                    const float s2 = (g1 * g1 + g2 * g2) * P.inv_mu_c2 + g3 * g3 * P.inv_mu_ct2;
+                    const float sc = clampf(fn * rsq(fmaxf(s2, 1e-30f)), 0.f, 1.f);
+                    const float d1 = g1 * sc - T.f[1], d2 = g2 * sc - T.f[2], d3 = g3 * sc - T.f[3];
+                    T.f[0] = fn; T.f[1] += d1; T.f[2] += d2; T.f[3] += d3;
+                    track(d0, d1, d2, d3, T.f[0], T.f[1], T.f[2], T.f[3]);
+                    const float la = minv * sg * d0, lb = minv * d1, lc = minv * sg * d2;
+                    const float aa = iinv * (-r.z * d1 + sg * r.y * d2 + sg * d3);
+                    const float ab = iinv * sg * (r.z * d0 - r.x * d2);
+                    const float ac = iinv * (-sg * r.y * d0 + r.x * d1);
+                    if (pr == 0) { ca[0] = ca[0] + mk(la, lb, lc); cal[0] = cal[0] + mk(aa, ab, ac); }
+                    else { ca[0] = ca[0] + mk(lc, la, lb); cal[0] = cal[0] + mk(ac, aa, ab); }
+                }
+            }
+            // arm-coupled slots: finger spheres, arm-link proxies
+            if (wave_arm) {
+#pragma unroll
+                for (int s = 0; s < NAS; s++) {
+                    if (!slot_any[s]) continue;
+                    ArmSlot<NRW> &T = AS[s];
+                    const bool may_cube = s < 2 || s == 4;
+                    const bool oncube = s < 2 || (s == 4 && link_on_cube);
+                    constexpr bool roll = ROLL;
+                    const int nrow = (roll && s < 2) ? 6 : 4;
+                    const float Rf = T.Rn * P.inv_impratio;
+                    const float Rt = Rf * (s < 2 ? P.rt_fc : (s < 4 ? RT_FF : P.rt_cube));
+                    // the six arm components travel as three float2 pairs: dot products and updates become v_pk_mul/v_pk_fma
+                    float2v g[NRW][3];
+#pragma unroll
+                    for (int r = 0; r < nrow; r++)
+#pragma unroll
+                        for (int k = 0; k < 3; k++)
+                            g[r][k] = (NC == 2 && !BIG && s == 4) ? *reinterpret_cast<const float2v *>(&P.scratch[((size_t)(r * 3 + k) * P.n + env) * 2])
+                                      : (NC == 2 && !BIG && r >= 4) ? *reinterpret_cast<const float2v *>(&P.scratch[((size_t)((4 + 2 * s + (r - 4)) * 3 + k) * P.n + env) * 2])
+                                                          : *reinterpret_cast<const float2v *>(&lds[(as_row0<ROLL, NC, BIG>(s) + r) * LDS_ROW + k * 128 + lane * 2]);
+                    float2v yp[3] = {{y[0], y[1]}, {y[2], y[3]}, {y[4], y[5]}};
+                    float arefv[NRW], invv[NRW], f_in[NRW];
+#pragma unroll
+                    for (int r = 0; r < NRW; r++) { arefv[r] = T.aref[r]; invv[r] = T.inv[r]; f_in[r] = T.f[r]; }
+                    // pick the cube this slot talks to (wave-divergent only for Stack)
+                    f3 a_lin = mk(0.f, 0.f, 0.f), a_ang = mk(0.f, 0.f, 0.f);
+                    const bool second = may_cube && NC == 2 && slot_cube[s == 4 ? 2 : (s & 1)] == 1;
+                    if (may_cube) { a_lin = second ? ca[NC - 1] : ca[0]; a_ang = second ? cal[NC - 1] : cal[0]; }
+                    // cube-side inverse inertia of this lane's contact (zero when the proxy slot touches the floor: the cube terms vanish)
+                    const float minv_e = (s == 4 && !oncube) ? 0.f : minv, iinv_e = (s == 4 && !oncube) ? 0.f : iinv;
+                    // The cube's share of the four row residuals is tracked as SCALARS: v_r = d_r . (acceleration of the contact
+                    // point of the cube), wn = n . (angular acceleration).  A force change dlt on row j moves them by closed-form
+                    // couplings, because (rc x d_i).(rc x d_j) = |rc|^2 delta_ij - (rc.d_i)(rc.d_j) for the orthonormal frame:
+                    //   v_i -= dlt (k delta_ij - iinv p_i p_j), k = minv + iinv |rc|^2, p_i = rc . d_i;   wn -= iinv dlt n.(rc x d_j)
+                    // and the summed force is applied to the cube once at the end of the slot.
+                    // (ROLL: the rolling rows need the angular acceleration about t1 and t2 as well: wq = (n, t1, t2) . alpha, wn = wq[0])
+                    float vq[3] = {0.f, 0.f, 0.f}, pq[3] = {0.f, 0.f, 0.f}, wn = 0.f, kq = 0.f, w1 = 0.f, w2 = 0.f;
+                    if (may_cube) {
+                        const f3 Ac = a_lin + cross(a_ang, T.rc);
+                        vq[0] = dot(T.n, Ac); vq[1] = dot(T.t1, Ac); vq[2] = dot(T.t2, Ac);
+                        pq[0] = dot(T.rc, T.n); pq[1] = dot(T.rc, T.t1); pq[2] = dot(T.rc, T.t2);
+                        wn = dot(T.n, a_ang);
+                        if (nrow == 6) { w1 = dot(T.t1, a_ang); w2 = dot(T.t2, a_ang); }
+                        kq = fmaf(iinv_e, dot(T.rc, T.rc), minv_e);
+                        if (s == 4) {   // floor lanes: no cube share in the residuals
+#pragma unroll
+                            for (int i = 0; i < 3; i++) vq[i] = oncube ? vq[i] : 0.f;
+                            wn = oncube ? wn : 0.f;
+                        }
+                    }
+                    // effect of a force change dlt on row j on the tracked scalars
+                    auto couple = [&](int j, float dlt) {
+                        if (j < 3) {
+                            const float c = iinv_e * pq[j] * dlt;
+#pragma unroll
+                            for (int i = 0; i < 3; i++) vq[i] = fmaf(c, pq[i], vq[i]);
+                            vq[j] = fmaf(-kq, dlt, vq[j]);
+                            // n.(rc x t1) = -rc.t2, n.(rc x t2) = rc.t1, n.(rc x n) = 0
+                            if (j == 1) wn = fmaf(iinv_e * dlt, pq[2], wn);
+                            if (j == 2) wn = fmaf(-iinv_e * dlt, pq[1], wn);
+                            if (nrow == 6) {   // d_i . (rc x d_j) = rc . (d_j x d_i), right-handed frame n x t1 = t2, t1 x t2 = n, t2 x n = t1
+                                if (j == 0) { w1 = fmaf(-iinv_e * dlt, pq[2], w1); w2 = fmaf(iinv_e * dlt, pq[1], w2); }
+                                if (j == 1) w2 = fmaf(-iinv_e * dlt, pq[0], w2);
+                                if (j == 2) w1 = fmaf(iinv_e * dlt, pq[0], w1);
+                            }
+                        } else if (j == 3) {   // torsion: angular acceleration changes by -iinv dlt n; contact point by (-iinv dlt n) x rc
+                            wn = fmaf(-iinv_e, dlt, wn);
+                            vq[1] = fmaf(iinv_e * dlt, pq[2], vq[1]);    // t1.(n x rc) = -p_2
+                            vq[2] = fmaf(-iinv_e * dlt, pq[1], vq[2]);   // t2.(n x rc) =  p_1
+                        } else if (j == 4) {   // rolling about t1: alpha -= iinv dlt t1; point acceleration += (-iinv dlt t1) x rc
+                            w1 = fmaf(-iinv_e, dlt, w1);
+                            vq[0] = fmaf(-iinv_e * dlt, pq[2], vq[0]);   // n.(t1 x rc)  =  p_2
+                            vq[2] = fmaf(iinv_e * dlt, pq[0], vq[2]);    // t2.(t1 x rc) = -p_0
+                        } else {               // rolling about t2
+                            w2 = fmaf(-iinv_e, dlt, w2);
+                            vq[0] = fmaf(iinv_e * dlt, pq[1], vq[0]);    // n.(t2 x rc)  = -p_1
+                            vq[1] = fmaf(-iinv_e * dlt, pq[0], vq[1]);   // t1.(t2 x rc) =  p_0
+                        }
+                    };
+#pragma unroll
+                    for (int r = 0; r < nrow; r++) {
+                        const float2v acc = g[r][0] * yp[0] + g[r][1] * yp[1] + g[r][2] * yp[2];
+                        const float gy = acc.x + acc.y;
+                        float jc_a = may_cube ? (r < 3 ? -vq[r] : -wn) : 0.f;
+                        float Rr = r == 0 ? T.Rn : (r == 3 ? Rt : Rf);
+                        if (ROLL && r > 3) { jc_a = r == 4 ? -w1 : -w2; Rr = Rf * P.rr_fc; }
+                        float res = gy + jc_a - arefv[r] + Rr * T.f[r];
+                        float nf = T.f[r] - res * invv[r];
+                        if (r == 0) nf = fmaxf(nf, 0.f);
+                        float dlt = nf - T.f[r];
+                        T.f[r] += dlt;
+                        {
+                            const float2v d2 = {dlt, dlt};
+#pragma unroll
+                            for (int k = 0; k < 3; k++) yp[k] = g[r][k] * d2 + yp[k];
+                        }
+                        if (may_cube) couple(r, dlt);
+                    }
+                    // cone projection (finger geoms: mu 1.5; a link proxy on the floor: mu 1; on a cube: the cube's friction)
+                    {
+                        float fn = T.f[0];
+                        const float imu2 = s < 4 ? 1.f / (MU_FINGER * MU_FINGER) : (oncube ? P.inv_mu_c2 : 1.f);
+                        const float imt2 = s < 2 ? P.inv_mu_fct2 : (s < 4 ? 1.f / (MU_TORS * MU_TORS) : P.inv_mu_ct2);
+                        float s2 = (T.f[1] * T.f[1] + T.f[2] * T.f[2]) * imu2 + (nrow >= 4 ? T.f[3] * T.f[3] * imt2 : 0.f);
+                        if constexpr (ROLL) { if (nrow == 6) s2 = fmaf(T.f[4] * T.f[4] + T.f[5] * T.f[5], P.inv_mu_fcr2, s2); }
+                        float sc = clampf(fn * rsq(fmaxf(s2, 1e-30f)), 0.f, 1.f);
+#pragma unroll
+                        for (int r = 1; r < nrow; r++) {
+                            float dlt = T.f[r] * sc - T.f[r];
+                            T.f[r] += dlt;
+                            const float2v d2 = {dlt, dlt};
+#pragma unroll
+                            for (int k = 0; k < 3; k++) yp[k] = g[r][k] * d2 + yp[k];
+                            // (the tracked scalars are not needed any more: the next slot starts from the updated accelerations)
+                        }
+                    }
+                    // (converged mode: the NET force change of this sweep, after the cone projection -- a sliding contact at its projected fixed
+                    //  point has a non-zero raw tangential update every sweep, which is then scaled back)
+                    track(T.f[0] - f_in[0], T.f[1] - f_in[1], T.f[2] - f_in[2], T.f[3] - f_in[3], T.f[0], T.f[1], T.f[2], T.f[3]);
+                    if constexpr (ROLL) { if (nrow == 6) track(T.f[4] - f_in[4], T.f[5] - f_in[5], 0.f, 0.f, T.f[4], T.f[5], 0.f, 0.f); }
+                    f3 dl_lin = mk(0.f, 0.f, 0.f), dl_ang = mk(0.f, 0.f, 0.f);  // change of the cube acceleration by this slot
+                    if (may_cube) {
+                        const float e0 = T.f[0] - f_in[0], e1 = T.f[1] - f_in[1], e2 = T.f[2] - f_in[2], e3 = T.f[3] - f_in[3];
+                        const f3 Fd = axpy(e0, T.n, axpy(e1, T.t1, e2 * T.t2));   // force change on the arm; the cube gets -Fd at rc
+                        dl_lin = (-minv_e) * Fd;
+                        f3 Td = axpy(e3, T.n, cross(T.rc, Fd));
+                        if constexpr (ROLL) { if (nrow == 6) Td = axpy(T.f[4] - f_in[4], T.t1, axpy(T.f[5] - f_in[5], T.t2, Td)); }
+                        dl_ang = (-iinv_e) * Td;
+                    }
+                    y[0] = yp[0].x; y[1] = yp[0].y; y[2] = yp[1].x; y[3] = yp[1].y; y[4] = yp[2].x; y[5] = yp[2].y;
+                    if (may_cube) {
+                        if (NC == 2) {
+                            if (second) { ca[NC - 1] = ca[NC - 1] + dl_lin; cal[NC - 1] = cal[NC - 1] + dl_ang; }
+                            else { ca[0] = ca[0] + dl_lin; cal[0] = cal[0] + dl_ang; }
+                        } else { ca[0] = ca[0] + dl_lin; cal[0] = cal[0] + dl_ang; }
+                    }
+                }
+            }
+        } else {
+            // group B, second part: finger<->cube
+            if constexpr (NC == 1) { arm_slot(std::integral_constant<int, 0>{}); arm_slot(std::integral_constant<int, 1>{}); }
+#pragma unroll
+            for (int c = 0; c < NC; c++) { ca[c] = ca[c] + dcaA[c]; cal[c] = cal[c] + dcalA[c]; }   // group A's share of the cube accelerations (slot 4)
+        }
         sweeps_done = it + 1;
         if (ADAPT) {
             if (__all(chg <= P.pgs_tol * (1.f + fmx))) break;
@@ -1276,6 +1625,7 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
 #pragma unroll
         for (int s = 0; s < NCC; s++) {
             if (NC == 2) m |= cc_act[s] ? (1u << (s < 4 ? 8 + s : 24 + (s - 4))) : 0u;
+            if (WALLS && s < 4) m |= WS[s].act ? (1u << (8 + s)) : 0u;
         }
         m |= AS[0].act ? (1u << 12) : 0u; m |= AS[1].act ? (1u << 13) : 0u;
         m |= AS[2].act ? (1u << 14) : 0u; m |= AS[3].act ? (1u << 15) : 0u;
@@ -1289,6 +1639,12 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
     }
 #pragma unroll
     for (int j = 0; j < 6; j++) W.lim[j] = flim[j];
+    if constexpr (WALLS) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) W.wall[s][k] = WS[s].f[k];
+    }
 
     // ---- implicitfast: (M + h (damping + kv) I) qacc = qfrc_smooth + J^T f = L y -------------------
     float rhs[6];
@@ -1340,12 +1696,12 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
 // ------------------------------------------------------------------------------------------------
 // the step kernel
 // ------------------------------------------------------------------------------------------------
-// (one cube + NEWTON: four waves per workgroup sharing a queue of cooperative solves, CoopQueue above; every other variant: one wave)
-template <int NC, bool EE, bool ADAPT, bool ROLL, bool BIG, bool NEWTON = false>
-__global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) void lcr_step_kernel(LcrDev P, const float *__restrict__ action) {
+// (one cube + NEWTON, no rails: four waves per workgroup sharing a queue of cooperative solves, CoopQueue above; every other variant: one wave)
+template <int NC, bool EE, bool ADAPT, bool ROLL, bool BIG, bool NEWTON = false, bool WALLS = false>
+__global__ __launch_bounds__((cq_kernel<NC, NEWTON, WALLS>() ? 64 * CQ_WAVES : 64)) void lcr_step_kernel(LcrDev P, const float *__restrict__ action) {
     constexpr int CCR = NEWTON ? CC_REC_NEWTON : CC_REC;
-    constexpr bool CQ = cq_kernel<NC, NEWTON>();
-    __shared__ float lds_wg[CQ ? CQ_FLOATS : (NEWTON ? NEWTON_G_ROWS * LDS_ROW + (NC == 2 ? 8 * CCR * 64 : 0) + coop_floats<NC>() : LdsSize<NC, false, ROLL, BIG>::value)];   // (NEWTON: 4 x 6 + 4 g rows = 33 KiB per wave, Stack + eight cube<->cube records of 12 floats = 66 KiB)
+    constexpr bool CQ = cq_kernel<NC, NEWTON, WALLS>();
+    __shared__ float lds_wg[CQ ? CQ_FLOATS : (NEWTON ? NEWTON_G_ROWS * LDS_ROW + (NC == 2 ? 8 * CCR * 64 : 0) + coop_floats<NC, WALLS>() : LdsSize<NC, WALLS, ROLL, BIG>::value)];   // (NEWTON: 4 x 6 + 4 g rows = 33 KiB per wave, Stack + eight cube<->cube records of 12 floats = 66 KiB)
     constexpr int NCC = NEWTON ? 8 : 4;
     constexpr int CCB = NEWTON ? NEWTON_G_ROWS : cc_base_rows<NC, BIG, ROLL>();
     const int lane = CQ ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
@@ -1372,6 +1728,7 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
     f3 target = mk(0.f, 0.f, 0.f);
     if (P.has_target) target = mk(P.target[e], P.target[N + e], P.target[2 * N + e]);
     int elapsed = P.elapsed[e];
+    int goal = WALLS ? P.goal[e] : 0;   // (PushCubeLoop: which goal side is active)
 
     // ---- apply_action (reach_cube_env.py:223-273) ------------------------------------------------
     float act[6];
@@ -1465,6 +1822,12 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
         for (int k = 0; k < (ROLL ? 6 : 4); k++) W.arm[s][k] = wld(WARM_ARM + 6 * s + k);
 #pragma unroll
     for (int j = 0; j < 6; j++) W.lim[j] = wld(WARM_LIM + j);
+    if constexpr (WALLS) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) W.wall[s][k] = wld(WARM_WALL + 4 * s + k);
+    }
 #pragma unroll
     for (int s = 0; s < 8; s++) W.cc_prev[s] = false;
     if constexpr (NC == 2) {   // cube<->cube forces live in their LDS records between substeps
@@ -1481,11 +1844,11 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
         // two copies of the substep (see CPL above): the wave runs the fast one while at most coop_max of its lanes are coupled, else the SIMT one
         bool slow = false;   // wave-uniform
         for (int s = 0; s < P.n_substeps; s++) {
-            if (!slow) slow = !substep<NC, ADAPT, ROLL, BIG, NEWTON, CPL_FAST>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
-            if (slow) slow = substep<NC, ADAPT, ROLL, BIG, NEWTON, CPL_SLOW>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
+            if (!slow) slow = !substep<NC, ADAPT, ROLL, BIG, NEWTON, CPL_FAST, WALLS>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
+            if (slow) slow = substep<NC, ADAPT, ROLL, BIG, NEWTON, CPL_SLOW, WALLS>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
         }
     } else {
-        for (int s = 0; s < P.n_substeps; s++) substep<NC, ADAPT, ROLL, BIG, NEWTON>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
+        for (int s = 0; s < P.n_substeps; s++) substep<NC, ADAPT, ROLL, BIG, NEWTON, CPL_BOTH, WALLS>(P, S, ctrl, lds, lane, e, lag_ee, lag_cube, W, DG, s);
     }
     if (P.diag && valid) {
         P.active_mask[e] = DG.mask; P.active_count[e] = DG.count; P.max_sweeps[e] = DG.sweeps;
@@ -1507,7 +1870,19 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
         else { a3 = lag_cube[0]; b3 = target; }
         f3 df = a3 - b3;
         float d = sqrtf(dot(df, df));
-        if (task == 1) {  // lift:341-345: (cube_z - height_threshold) + distance, never terminates, info = {}
+        if (WALLS && task == 5) {  // PushCubeLoop get_reward / get_cube_overlap (push_cube_loop_env.py:334-383), FRESH cube position
+            const float xc = S.cp[0].x, yc = S.cp[0].y, wc = 0.0075f;            // cube_size = 0.015 / 2 (:124)
+            const float gx = goal ? -0.06f : 0.06f, gy = 0.135f;                 // push_cube_loop.xml:38,41
+            const float gh0 = 0.0095f, gh1 = 0.0145f;                            // goal_region_high[:2] (:133-134)
+            const float xo = fmaxf(0.f, fminf(xc + wc, gx + gh0) - fmaxf(xc - wc, gx - gh0));
+            const float yo = fmaxf(0.f, fminf(yc + wc, gy + gh1) - fmaxf(yc - wc, gy - gh1));
+            const float overlap = xo * yo * (1.f / (4.f * 0.0075f * 0.0075f));
+            success = overlap > 0.95f;
+            terminated = false;
+            const float edge = -gh1 + gy;
+            reward = success ? 5.f : (overlap > 0.f ? overlap - 1.f : clampf(-fabsf(yc - edge) * (1.f / 0.16f) - 1.f, -2.f, -1.f));
+            if (success) goal = 1 - goal;                                         // the goal side switches and PERSISTS (:341)
+        } else if (task == 1) {  // lift:341-345: (cube_z - height_threshold) + distance, never terminates, info = {}
             reward = (lag_cube[0].z - P.height_thr) + d;
             success = false; terminated = false;
         } else {
@@ -1550,7 +1925,7 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
                 for (int k = 0; k < 4; k++) P.term_quat[(size_t)(4 * c + k) * N + e] = S.cq[c][k];   // completes the terminal pose (frames of recordings)
         }
         Pcg g = load_rng(P, e);
-        reset_env<NC>(P, S, g, target, lag_ee, 0);
+        reset_env<NC>(P, S, g, target, lag_ee, goal);
         if (diverged) {
 #pragma unroll
             for (int j = 0; j < 6; j++) S.qd[j] = 0.f;
@@ -1567,6 +1942,7 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
         store_state<NC>(P, e, S);
         P.elapsed[e] = elapsed;
         P.ee_lag[e] = lag_ee.x; P.ee_lag[N + e] = lag_ee.y; P.ee_lag[2 * N + e] = lag_ee.z;
+        if (WALLS) P.goal[e] = goal;
         if (P.sim_time) P.sim_time[e] = __dadd_rn(P.sim_time[e], (double)P.n_substeps * 0.002);  // data.time advances in mj_step only
     }
     if (carry && valid) {   // forces for the next control step's first substep; an env that was just reset starts from zero
@@ -1583,6 +1959,12 @@ __global__ __launch_bounds__((cq_kernel<NC, NEWTON>() ? 64 * CQ_WAVES : 64)) voi
             for (int k = 0; k < (ROLL ? 6 : 4); k++) wst(WARM_ARM + 6 * s + k, W.arm[s][k]);
 #pragma unroll
         for (int j = 0; j < 6; j++) wst(WARM_LIM + j, W.lim[j]);
+        if constexpr (WALLS) {
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) wst(WARM_WALL + 4 * s + k, W.wall[s][k]);
+        }
         if constexpr (NC == 2) {
             const float *ccl = lds + CCB * LDS_ROW + lane;
 #pragma unroll
@@ -1679,10 +2061,10 @@ static int check_launch() {
     return err == hipSuccess ? 0 : (int)err;
 }
 
-// The step kernel has 24 instantiations.  gym_lowcostrobot_amd/build.py compiles this file three times in parallel, -DLCR_PART=0|2|3
-// selecting which launchers -- and hence which instantiations -- a translation unit emits: 0 the one-cube kernels (+ the dispatcher and
-// the small kernels), 2 / 3 the two StackTwoCubes variants.  Without the macro (tools/) everything is in one unit.  (PushCubeLoop:
-// lcr_kernels_loop.hip.)
+// The step kernel has 38 instantiations.  gym_lowcostrobot_amd/build.py compiles this file seven times in parallel, -DLCR_PART=0|2|3|4|5|6|7
+// selecting which launchers -- and hence which instantiations -- a translation unit emits: 0 the one-cube sweep kernels (+ the dispatcher and
+// the small kernels), 2 / 3 the two StackTwoCubes variants, 4 / 5 the Newton kernels of one cube / StackTwoCubes, 6 / 7 PushCubeLoop's sweep /
+// Newton kernels.  Without the macro (tools/) everything is in one unit.
 // the four solver-mode / contact-row variants of one launcher
 #define LCR_DISPATCH_MODES(fn)                                              \
     do {                                                                    \
@@ -1697,6 +2079,7 @@ static int check_launch() {
 
 int lcr_launch_step_stack(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st);
 int lcr_launch_step_stack_big(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st);
+int lcr_launch_step_loop(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st);
 
 #if LCR_HAS_PART(2)
 template <bool ADAPT, bool ROLL>
@@ -1746,6 +2129,29 @@ int lcr_launch_step_newton_stack(const LcrDev &P, const float *action_dev, int e
 }
 #endif
 
+#if LCR_HAS_PART(6)
+template <bool ADAPT, bool ROLL>
+static void launch_loop_t(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st) {   // PushCubeLoop: the rails, row-wise sweeps
+    const int blocks = (P.n + 63) / 64;
+    if (!ee_mode) hipLaunchKernelGGL((lcr_step_kernel<1, false, ADAPT, ROLL, false, false, true>), dim3(blocks), dim3(64), 0, st, P, action_dev);
+    else hipLaunchKernelGGL((lcr_step_kernel<1, true, ADAPT, ROLL, false, false, true>), dim3(blocks), dim3(64), 0, st, P, action_dev);
+}
+int lcr_launch_step_loop(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st) {
+    LCR_DISPATCH_MODES(launch_loop_t);
+    return check_launch();
+}
+#endif
+
+#if LCR_HAS_PART(7)
+int lcr_launch_step_loop_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream) {   // one wave per workgroup (no CoopQueue)
+    const int blocks = (P.n + 63) / 64;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!ee_mode) hipLaunchKernelGGL((lcr_step_kernel<1, false, false, true, false, true, true>), dim3(blocks), dim3(64), 0, st, P, action_dev);
+    else hipLaunchKernelGGL((lcr_step_kernel<1, true, false, true, false, true, true>), dim3(blocks), dim3(64), 0, st, P, action_dev);
+    return check_launch();
+}
+#endif
+
 #if LCR_HAS_PART(0)
 template <bool ADAPT, bool ROLL>
 static void launch_one_cube_t(const LcrDev &P, const float *action_dev, int ee_mode, hipStream_t st) {
@@ -1755,8 +2161,11 @@ static void launch_one_cube_t(const LcrDev &P, const float *action_dev, int ee_m
 }
 int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
-    if (P.walls) return lcr_launch_step_loop(P, action_dev, ee_mode, stream);   // PushCubeLoop: its own unit and solver (lcr_kernels_loop.hip)
-    if (P.newton) return P.task == 4 ? lcr_launch_step_newton_stack(P, action_dev, ee_mode, stream) : lcr_launch_step_newton(P, action_dev, ee_mode, stream);
+    if (P.newton) {
+        if (P.walls) return lcr_launch_step_loop_newton(P, action_dev, ee_mode, stream);
+        return P.task == 4 ? lcr_launch_step_newton_stack(P, action_dev, ee_mode, stream) : lcr_launch_step_newton(P, action_dev, ee_mode, stream);
+    }
+    if (P.walls) return lcr_launch_step_loop(P, action_dev, ee_mode, st);   // PushCubeLoop: one wave per 64 envs, its row-wise solver
     if (P.coop && P.pgs_iters >= 0 && P.diag != 2) {   // two cooperating waves per 64 envs (no converged mode, no per-wave cycle read-back)
         if (P.task == 4) return P.cc8 ? lcr_launch_step2_stack_cc8(P, action_dev, ee_mode, P.coop, stream) : lcr_launch_step2_stack(P, action_dev, ee_mode, P.coop, stream);
         return lcr_launch_step2_one_cube(P, action_dev, ee_mode, P.coop, stream);

@@ -31,7 +31,7 @@
 //
 // At 32 768 envs per GPU the 1024 waves occupy all 1024 SIMDs (one each, up to 512 registers per lane: variant OCC = 1, what lcr_create
 // dispatches for such shards); at 65 536 envs two waves share a SIMD (<= 256 registers per lane, variant OCC = 2: same source, same bits;
-// since round 4 faster than the one-wave kernels for every one-cube task -- DESIGN.md section 5; PushCubeLoop: lcr_kernels_loop.hip).
+// since round 4 faster than the one-wave kernels for every one-cube task -- DESIGN.md section 5; PushCubeLoop: lcr_kernels.hip, WALLS).
 //
 // Reference map: identical to lcr_kernels.hip (apply_action reach_cube_env.py:223-273, 20 x mj_step :276-279, reward / termination
 // :313-348 and the per-task files, reset :297-311); the arithmetic of every block is the one of lcr_kernels.hip, regrouped by owner.

@@ -161,7 +161,7 @@ struct NewtonCtx {
     bool link_on_cube;
     const int (&slot_cube)[3];
     FloorSlot (&FS)[NC][4];
-    FloorSlot (&WS)[4];          // PushCubeLoop rails (lcr_kernels_loop.hip), pair coordinates
+    FloorSlot (&WS)[4];          // PushCubeLoop rails (lcr_kernels.hip, WALLS), pair coordinates
     const float (&wsg)[2];
     bool wall_any;
     float *ccl;                  // StackTwoCubes: cube<->cube records in LDS, field k of slot s at ccl[(s * CC_REC_NEWTON + k) * 64]

@@ -65,7 +65,7 @@ DEV float impedance(float dist, float d0, float dw, float inv_width) {
 // All rows of a block are evaluated from the same forces: no serial dependence inside a block.  In force units, select-free:
 //     f_n' = f_n - u_n iLn,  f_j' = f_j - (mu_j^2 iLt) u_j,  N = |(f_j' / mu_j)|,  f_n = max(f_n', w f_n' + (1 - w) N, 0),  f_j = f_j' min(1, f_n / N)
 // k[0] = iLn, k[1] = mu_tan^2 iLt, k[2] = w, k[3] = mu_tors^2 iLt (, k[4] = mu_roll^2 iLt); a block that is off has k = 0 and f = 0: its updates are exact zeros.
-// PushCubeLoop keeps the row-wise sweeps (lcr_kernels_loop.hip): its cube has torsional and rolling coefficients of 1.5 m (push_cube_loop.xml:31) whose scaled curvature
+// PushCubeLoop keeps the row-wise sweeps (lcr_kernels.hip, WALLS): its cube has torsional and rolling coefficients of 1.5 m (push_cube_loop.xml:31) whose scaled curvature
 // mu^2 / I would set Lt, i.e. the step of every friction row of the block.
 template <int NR>
 DEV void soc_step(const float (&f)[NR], const float (&u)[NR], const float (&k)[NR], float im_tan2, float im_tors2, float im_roll2, int nrow, float (&nf)[NR]) {

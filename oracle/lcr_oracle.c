@@ -1922,7 +1922,7 @@ static void params_base(orc_params *p, int task) {   /* the reference's construc
     p->pgs_tol = 1e-6;
     p->cc_points = 4;
     /* what the kernels run: block projected gradient in the second-order-cone variables with the rows in two concurrently swept groups (round 4) -- except
-     * PushCubeLoop, which keeps the row-wise Gauss-Seidel sweeps with the radial projection, one sequence (lcr_kernels_loop.hip; deviation D2) */
+     * PushCubeLoop, which keeps the row-wise Gauss-Seidel sweeps with the radial projection, one sequence (lcr_kernels.hip, WALLS; deviation D2) */
     p->cone = task == ORC_TASK_PUSH_LOOP ? 0 : 3;
     p->pgs_cap = 0;   /* 50 */
     p->solver = 0;    /* PGS (what the kernels run) */

@@ -986,7 +986,7 @@ def test_kernel_families_agree_and_are_race_free(hip_lib, kernel_family, monkeyp
     states to the same result within fp32 rounding (they group the same arithmetic differently), take the same discrete decisions, and
     the two-wave kernels give the same bits run after run (their LDS hand-overs between the arm wave and the cube wave are ordered by
     barriers: a missing one shows up as run-to-run differences -- found once, in round 3's two-wave PushCubeLoop kernel; that task has one kernel since
-    round 4, lcr_kernels_loop.hip)"""
+    round 4, lcr_kernels.hip, WALLS)"""
     _sweeps_only(kernel_family)
     n = 4096
     sims = {}
