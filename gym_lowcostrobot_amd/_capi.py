@@ -11,7 +11,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LCR_LIB_PATH") or os.path.join(_HERE, "liblcr_hip.so")  # override: A/B builds of the same ABI
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 NWARM = 124   # LCR_NWARM: floats per env of carried constraint forces (layout: include/lcr.h)
 TASKS = {"reach": 0, "lift": 1, "push": 2, "pick_place": 3, "stack": 4, "push_loop": 5}
 ACTION_MODES = {"joint": 0, "ee": 1}
@@ -24,7 +24,7 @@ COOP_SHARE = {None: 0, "owner": 1, "shared": 2, "handoff": 3}   # lcr_config.coo
 PROFILE_MODES = {None: None, "wave_cycles": 2, "phase_cycles": 3}   # lcr_config.diagnostics values 2, 3 (per-wave cycle read-back; see include/lcr.h)
 COMPAT_ZERO_QVEL_ON_RESET = 1
 COMPAT_COLD_SOLVE_EACH_STEP = 2   # contact solver starts every control step from zero forces (default: forces carried across steps)
-IMG_H, IMG_W = 240, 320
+IMG_H, IMG_W = 240, 320   # LCR_IMG_H / LCR_IMG_W: the default size of the image observations (lcr_config.image_width = image_height = 0)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
@@ -75,6 +75,8 @@ class LcrConfig(ctypes.Structure):
         ("newton_tol", ctypes.c_double),
         ("ls_tol", ctypes.c_double),
         ("coop_share", ctypes.c_int32),    # ABI v6: COOP_SHARE
+        ("image_width", ctypes.c_int32),   # ABI v7: size of the image observations, multiples of 4 in [16, 512]; 0, 0 = 320 x 240
+        ("image_height", ctypes.c_int32),
     ]
 
 
@@ -88,6 +90,8 @@ class LcrObsView(ctypes.Structure):
         ("aux_pos", ctypes.c_void_p),
         ("image_front", ctypes.c_void_p),
         ("image_top", ctypes.c_void_p),
+        ("image_width", ctypes.c_int32),   # ABI v7: the size in use (0, 0 without images)
+        ("image_height", ctypes.c_int32),
     ]
 
 

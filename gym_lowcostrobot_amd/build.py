@@ -32,7 +32,9 @@ def _newer(target, deps):
 # Newton kernels) -- kernels of ~50-100 KB code each: 80 s in one unit, ~30 s as units compiled concurrently
 NO_POST_RA = ["-mllvm", "-enable-post-misched=0"]
 ITER_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-UNITS = [("lcr_capi.hip", "lcr_capi.o", []), ("lcr_render.hip", "lcr_render.o", []),
+UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
+         # the frame kernels: the default 320 x 240 build (+ background, single-frame and gather kernels) and the builds for run-time sizes, a code object each (lcr_render.hip)
+         ("lcr_render.hip", "lcr_render.o", ["-DLCR_RENDER_PART=0"]), ("lcr_render.hip", "lcr_render_sizes.o", ["-DLCR_RENDER_PART=1"]),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),
@@ -57,6 +59,9 @@ def build(force=False, verbose=False):
     if not os.path.exists(hipcc):
         hipcc = "hipcc"
     deps = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]   # (the per-unit flags live in this file)
+    # a tree that carries the library but not the objects (a source snapshot shipped with its .so) is current when the .so is newer than everything it is made of
+    if not force and os.path.exists(LIB) and not _newer(LIB, [os.path.join(CSRC, src) for src in SOURCES] + deps):
+        return LIB
     objs, jobs = [], []
     for src, obj, extra in UNITS:
         s = os.path.join(CSRC, src)

@@ -48,14 +48,14 @@ void cam_finish(LcrCam &c, const double p[3], double X[3], double Y[3], int heig
     c.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);  // MuJoCo default camera fovy = 45 deg
 }
 // cameras of the scene files (reach_cube.xml:29-31 and siblings)
-void make_cameras(int task, LcrCam &front, LcrCam &top, LcrCam &vizu) {
+void make_cameras(int task, int img_h, LcrCam &front, LcrCam &top, LcrCam &vizu) {
     {   // camera_front pos="0.049 0.5 0.225" xyaxes="-0.998 0.056 -0.000 -0.019 -0.335 0.942"
         double p[3] = {0.049, 0.5, 0.225}, X[3] = {-0.998, 0.056, -0.000}, Y[3] = {-0.019, -0.335, 0.942};
-        cam_finish(front, p, X, Y, LCR_IMG_H);
+        cam_finish(front, p, X, Y, img_h);
     }
     {   // camera_top pos="0 0.1 0.6" euler="0 0 0"
         double p[3] = {0, 0.1, 0.6}, X[3] = {1, 0, 0}, Y[3] = {0, 1, 0};
-        cam_finish(top, p, X, Y, LCR_IMG_H);
+        cam_finish(top, p, X, Y, img_h);
     }
     {   // camera_vizu pos="-0.2 0.6 0.3" (reach) / "-0.1 0.6 0.3" (others) quat="-0.15 -0.1 0.6 1"
         double p[3] = {task == LCR_TASK_REACH ? -0.2 : -0.1, 0.6, 0.3};
@@ -209,6 +209,10 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     if (cfg->finger_cube_condim != 0 && cfg->finger_cube_condim != 4 && cfg->finger_cube_condim != 6) return fail(LCR_ERR_INVALID, "finger_cube_condim must be 4 or 6");
     if (cfg->cc_points != 0 && cfg->cc_points != 4 && cfg->cc_points != 8) return fail(LCR_ERR_INVALID, "cc_points must be 4 or 8");
     if (cfg->coop_share < 0 || cfg->coop_share > 3) return fail(LCR_ERR_INVALID, "coop_share must be 0 (default), 1 (owner only), 2 (shared) or 3 (always hand off)");
+    // frame size: both zero (320 x 240) or each a multiple of 4 in [16, 512] (lcr.h: 16-byte aligned bands, one 32-bit mask of tile columns); checked whatever obs_mode is
+    if ((cfg->image_width == 0) != (cfg->image_height == 0)) return fail(LCR_ERR_INVALID, "image_width and image_height must both be 0 (320 x 240) or both be set (got %d x %d)", cfg->image_width, cfg->image_height);
+    if (cfg->image_width != 0 && (cfg->image_width < 16 || cfg->image_width > 512 || cfg->image_width % 4 != 0)) return fail(LCR_ERR_INVALID, "image_width must be a multiple of 4 in [16, 512] (got %d)", cfg->image_width);
+    if (cfg->image_height != 0 && (cfg->image_height < 16 || cfg->image_height > 512 || cfg->image_height % 4 != 0)) return fail(LCR_ERR_INVALID, "image_height must be a multiple of 4 in [16, 512] (got %d)", cfg->image_height);
     if (cfg->cc_points == 8 && cfg->task != LCR_TASK_STACK) return fail(LCR_ERR_INVALID, "cc_points = 8 is the cube<->cube manifold of StackTwoCubes; this task has one cube");
     if (cfg->cc_points == 8 && cfg->pgs_iters < 0) return fail(LCR_ERR_UNSUPPORTED, "cc_points = 8 is implemented by the two-wave kernels, the converged solver mode (pgs_iters < 0) by the one-wave kernels");
     if (cfg->step_kernel < 0 || cfg->step_kernel > 2) return fail(LCR_ERR_INVALID, "step_kernel must be 0 (by task and job size), 1 (one wave per 64 envs) or 2 (two cooperating waves)");
@@ -306,7 +310,8 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     size_t o_mask = off; off += al(N);
     size_t o_seeds = off; off += al(sizeof(unsigned long long) * N);
     size_t o_img0 = off, o_img1 = off;
-    const size_t img_bytes = (size_t)LCR_IMG_H * LCR_IMG_W * 3;
+    const int img_w = cfg->image_width ? cfg->image_width : LCR_IMG_W, img_h = cfg->image_height ? cfg->image_height : LCR_IMG_H;
+    const size_t img_bytes = (size_t)img_h * img_w * 3;
     size_t o_bg = off;
     if (s->has_images) { o_img0 = off; off += al(img_bytes * N); o_img1 = off; off += al(img_bytes * N); o_bg = off; off += al(2 * img_bytes); }
     s->arena_bytes = off;
@@ -451,7 +456,10 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     D.img_front = s->has_images ? (unsigned char *)(base + o_img0) : nullptr;
     D.img_top = s->has_images ? (unsigned char *)(base + o_img1) : nullptr;
     D.img_bg = s->has_images ? (unsigned char *)(base + o_bg) : nullptr;
-    make_cameras(cfg->task, s->cam_front, s->cam_top, s->cam_vizu);
+    D.img_w = img_w; D.img_h = img_h;
+    D.img_epw = lcr_render_envs_per_workgroup(img_w, img_h);
+    if (const char *ov = getenv("LCR_RENDER_EPW")) { const int v = atoi(ov); if (v == 1 || v == 2 || v == 4) D.img_epw = v; }   // (measurement: tools/frame_sizes.py; frames wider than 170 px have the one mapping)
+    make_cameras(cfg->task, img_h, s->cam_front, s->cam_top, s->cam_vizu);
     s->render_dev = nullptr;
     s->render_bytes = 0;
     s->term_stage = nullptr;
@@ -598,6 +606,8 @@ int lcr_get_obs(lcr_sim *s, lcr_obs_view *out) {
     else { out->has_aux = 0; out->aux_pos = nullptr; }
     out->image_front = s->dev.img_front;
     out->image_top = s->dev.img_top;
+    out->image_width = s->has_images ? s->dev.img_w : 0;
+    out->image_height = s->has_images ? s->dev.img_h : 0;
     return LCR_OK;
 }
 
@@ -819,9 +829,10 @@ int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint
     if (!s->has_images) return fail(LCR_ERR_UNSUPPORTED, "terminal frames need observation_mode image / both (the frame background is only kept then)");
     for (int i = 0; i < count; i++)
         if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
-    const size_t img = (size_t)LCR_IMG_H * LCR_IMG_W * 3;
-    const int CHUNK = 1024;   // envs per pass: 2 x 225 KiB of frames each -> at most 450 MiB of staging
-    const int cap = count < CHUNK ? count : CHUNK;
+    const size_t img = (size_t)s->dev.img_h * s->dev.img_w * 3;
+    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass: 1 024 envs at 320 x 240 (2 x 225 KiB each), 19 200 at 64 x 64
+    const size_t chunk = BUDGET / (2 * img);
+    const int cap = (size_t)count < chunk ? count : (int)chunk;
     if (cap == 0) return LCR_OK;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_ids = 0, o_q = al(sizeof(int) * cap), o_t = o_q + al(sizeof(float) * s->nq * cap), o_f = o_t + al(sizeof(float) * 3 * cap),

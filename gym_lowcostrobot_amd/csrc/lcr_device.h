@@ -53,8 +53,8 @@ struct LcrDev {
     float *ctrl_out;  // [6][n] actuator targets of the last step (diag != 0)
     float *scratch;   // one-wave Stack kernels: g rows of the arm-link proxy slot, [12][n] float2; two-wave kernels at two waves per SIMD: Wm records, [groups][64][36]
     // image observations
-    unsigned char *img_front, *img_top;  // [n][240][320][3] or null
-    unsigned char *img_bg;               // [2][240][320][3] env-independent background of camera_front / camera_top, or null
+    unsigned char *img_front, *img_top;  // [n][img_h][img_w][3] or null
+    unsigned char *img_bg;               // [2][img_h][img_w][3] env-independent background of camera_front / camera_top, or null
     // (appended: the offsets of everything above are what the tuned default kernels were compiled against)
     float rr_fc;         // finger<->cube: mu_tan^2 / mu_roll^2   (ROLL kernels: lcr_config.finger_cube_condim = 6)
     float inv_mu_fcr2;   // finger<->cube: 1 / mu_roll^2
@@ -74,6 +74,8 @@ struct LcrDev {
     int coop_max;                    // Newton kernels: a wave solves up to this many coupled (arm on cube, cube on cube) envs one by one with all its lanes (lcr_newton_coop.h); more: the 12-dimensional SIMT solve
     int coop_share;                  // one-cube Newton kernel: who solves a wave's coupled envs -- 0 the owning wave only, 1 any wave of the workgroup, the owner first (default),
                                      // 2 never the owner (lcr_config.coop_share - 1; lcr_kernels.hip: CoopQueue)
+    int img_w, img_h;                // size of the image observations (lcr_config.image_width / image_height; 320 x 240 by default)
+    int img_epw;                     // frame kernel: envs per workgroup (1, 2 or 4), chosen from the frame size at lcr_create (lcr_render.hip)
 };
 
 // pinhole camera: position, world axes (camera looks along -Z), s = 2 tan(fovy/2) / height
@@ -98,6 +100,7 @@ int lcr_launch_reset(const LcrDev &P, const unsigned char *mask_dev, const unsig
 int lcr_launch_fill_actions(float *action_dev, int n, int k, long long env_off, unsigned long long seed,
                             unsigned long long step, void *stream);
 int lcr_launch_render_obs(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream);
+int lcr_render_envs_per_workgroup(int W, int H);   // the frame kernel's mapping for a frame size
 int lcr_launch_gather_terminal(const LcrDev &P, const int *ids_dev, int count, float *qpos_out, float *target_out, void *stream);
 int lcr_launch_render_bg(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream);
 int lcr_launch_render_single(const LcrDev &P, const LcrCam &cam, int env, int W, int H, unsigned char *out_dev, void *stream);

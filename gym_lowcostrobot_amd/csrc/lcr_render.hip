@@ -1,4 +1,4 @@
-// lcr_render.hip -- image observations: a small ray-caster for the two 240x320 observation cameras of every env
+// lcr_render.hip -- image observations: a small ray-caster for the two observation cameras of every env (240x320 unless lcr_config.image_width / image_height say otherwise)
 // (get_observation, envs/reach_cube_env.py:288-292: renderer.update_scene(camera="camera_front"/"camera_top"); render())
 // and for the 640x640 `camera_vizu` frame of render() (envs/reach_cube_env.py:350-355).
 //
@@ -8,8 +8,8 @@
 // hulls (base_link, link_1 .. link_6: mesh extents of the golden model file, follower.xml:54-97; the 20 STL meshes themselves are not shipped; rounds 1-4
 // drew capsules between the link origins), ambient 0.3 + headlight 0.6 Lambert shading, no shadows.
 //
-// Mapping: a workgroup owns one env's 480 image rows (both frames); a wave handles one BAND of 4 rows at a time and writes its 3 840
-// bytes with non-temporal 16-B stores.  What does not depend on the env -- floor, sky and the arm's base -- is rendered once into a
+// Mapping: a workgroup owns one env's 2 H image rows (both frames; small frames: up to four envs); a wave handles one BAND of 4 rows at a time and writes its 12 W
+// bytes (3 840 at 320 wide) with non-temporal 16-B stores.  What does not depend on the env -- floor, sky and the arm's base -- is rendered once into a
 // cached frame pair, and bands no other primitive touches are plain copies of it.  The per-env scene (FK of the arm, cube frames, per camera the
 // ray-test constants and the screen-space silhouette of every primitive) is built once per workgroup in LDS; culling is wave-uniform (per band and
 // 16-pixel column), only 16 x 4 tiles that a silhouette touches are ray-cast.
@@ -21,6 +21,12 @@
 #include "lcr_device.h"
 
 using namespace lcrdev;
+
+// This file is compiled as two units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes; undefined =
+// everything in one unit (the tools that compile this file on its own)
+#ifndef LCR_RENDER_PART
+#define LCR_RENDER_PART 2
+#endif
 
 namespace {
 
@@ -189,6 +195,7 @@ DEV bool box_hit(const float *c, float sx, float sy, float tlimit, float &tmin, 
     return tmin <= tmax && tmin > 0.f && tmin < tlimit;
 }
 
+#if LCR_RENDER_PART != 1   // (the per-pixel shading of the background and single-frame kernels)
 DEV f3 floor_or_sky(f3 ro, f3 d, float inv_len, float &tfloor) {
     // checker floor below the horizon (builtin checker, 0.1 m squares; its normal is +z so the Lambert term is -d_z / |d|), gradient sky above (unshaded)
     const float rdz = d.z * inv_len;
@@ -222,6 +229,8 @@ DEV f3 shade_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, int
     return out;
 }
 
+#endif
+
 // One tile of an observation band: ray-cast the boxes of mask `m` (wave-uniform).  The staged rows already hold the background (floor, sky, base), so a
 // lane only reports a colour when its ray hits something else.  `stpx` = this pixel's 3 staged background bytes (read for the translucent target marker
 // only).  Returns true and sets rgb when the pixel has to be rewritten.
@@ -252,10 +261,11 @@ DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float 
     return draw;
 }
 
+#if LCR_RENDER_PART != 1
 // background frames of the two observation cameras -- checker floor, sky and the arm's base: identical for every env and every step, so they
-// are rendered ONCE at lcr_create into P.img_bg ([2][240][320][3], 460 800 B, L2-resident) and copied band-wise afterwards.
+// are rendered ONCE at lcr_create into P.img_bg ([2][H][W][3]; 460 800 B at 320 x 240, L2-resident) and copied band-wise afterwards.
 __global__ __launch_bounds__(256) void lcr_render_bg_kernel(LcrDev P, LcrCam front, LcrCam top) {
-    const int W = 320, H = 240;
+    const int W = P.img_w, H = P.img_h;
     const int pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= 2 * W * H) return;
     const bool is_top = pix >= W * H;
@@ -274,6 +284,8 @@ __global__ __launch_bounds__(256) void lcr_render_bg_kernel(LcrDev P, LcrCam fro
     P.img_bg[3 * (size_t)pix + 2] = (unsigned char)(rgb >> 16);
 }
 
+#endif
+
 // OR of a value over lanes 0 .. 15 (the primitives live in lanes 0 .. NPRIM-1): four row_shr DPP steps, the result is read from lane 15
 DEV unsigned or_row0(unsigned x) {
     x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
@@ -287,10 +299,16 @@ DEV unsigned or_row0(unsigned x) {
 // active_count / choice / max_sweeps (tools/render_work.py)
 // Six waves per SIMD: the 80 registers that takes spill six values of the scene set-up (the chain of link frames), none in the band loop (measured, 32 768 envs:
 // 5 waves 2.88 ms, 6: 2.77, 7: 2.92, 8: 2.95; the rounds 1-4 structure with its background prefetch in registers ran 4).
-template <bool COUNT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void lcr_render_obs_kernel(LcrDev P, LcrCam front, LcrCam top) {
-    // A workgroup owns one env (480 rows: front frame then top frame); a wave handles one BAND of 4 rows at a time (3 840 B = 240 lanes x
-    // 16 B).  The band starts as a copy of the cached background band (L2 hit); if no primitive's silhouette touches
+//
+// The frame size: TW x TH when they are given (320 x 240, the default: every extent a compile-time constant, the staging rows a static array), else P.img_w x P.img_h
+// (lcr_config.image_width / image_height: multiples of 4 in [16, 512]) with the staging rows in dynamic LDS (4 waves x 12 W bytes: six workgroups per CU fit up to
+// 320 wide, five at 512 -- the NV = 6 build is compiled for five waves per SIMD).  NV = 16-B vectors of a band (3 W / 4 of them) a lane carries, ceil(3 W / 256).
+// EPW = envs per workgroup (1, 2, 4), the mapping for small frames: 4 / EPW waves per env -- 4: two per camera, alternate bands; 2: one per camera; 1: one wave draws
+// both frames of its env -- so that the scene set-up of EPW envs runs side by side and a workgroup lives EPW times longer against its launch.
+template <bool COUNT, int NV, int EPW, int TW, int TH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 : 6, NV > 4 ? 5 : 6))) void lcr_render_obs_kernel(LcrDev P, LcrCam front, LcrCam top) {
+    // A workgroup owns EPW envs (one: 2 H rows, front frame then top frame); a wave handles one BAND of 4 rows at a time (12 W B = 3 W / 4 lanes x
+    // 16 B; 3 840 B = 240 lanes at 320 wide).  The band starts as a copy of the cached background band (L2 hit); if no primitive's silhouette touches
     // it (wave-uniform) it leaves straight away as non-temporal 16-B stores.  Otherwise the band is
     // staged in LDS, its 16 x 4-pixel tiles that a silhouette touches are ray-cast and
     // overwrite their bytes, and the band is stored from LDS.  No software prefetch across bands and the culling records in LDS rather than in
@@ -298,43 +316,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
     // other waves ray-cast.
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    constexpr int W = 320, H = 240, NT = W / 16;
+    constexpr bool FIXED = TW != 0;
+    static_assert(!FIXED || (TW % 16 == 0 && TH % 4 == 0 && (3 * TW / 4 + 63) / 64 == NV), "a fixed size has whole tile columns and its own NV");
+    static_assert(EPW == 1 || EPW == 2 || EPW == 4, "1, 2 or 4 waves per env");
+    const int W = FIXED ? TW : P.img_w, H = FIXED ? TH : P.img_h;
+    const int NT = (W + 15) >> 4;   // 16-pixel tile columns, the last one partial when W % 16 != 0 (<= 32: one mask word)
+    const int VB = 3 * W / 4;       // 16-B vectors of a band
+    const int RB = 3 * W;           // bytes of a row
     static_assert(NPRIM <= 16, "one primitive per lane of a DPP row");
-    __shared__ Scene S;
-    __shared__ __attribute__((aligned(16))) unsigned char stage[4][4 * 960];
-    const int env = blockIdx.x;
-    if (threadIdx.x == 0) build_scene(P, env, S);
+    __shared__ Scene S_[EPW];
+    __shared__ __attribute__((aligned(16))) unsigned char stage_fixed[FIXED ? 4 * 12 * TW : 16];
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage_dyn[];   // [4][12 W] when the size is a run-time value
+    constexpr int WPE = 4 / EPW;   // waves per env
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int e = wave / WPE, wsub = wave % WPE;
+    const int env = blockIdx.x * EPW + e;
+    const bool live = env < P.n;   // (a ragged batch: the waves of the missing envs only keep the barriers company)
+    Scene &S = S_[e];
+    const int tl = EPW == 1 ? (int)threadIdx.x : (int)threadIdx.x & (64 * WPE - 1);   // thread within its env's waves
+    if (tl == 0 && live) build_scene(P, env, S);
     __syncthreads();
-    if (threadIdx.x < 2 * NPRIM) {
-        const int cam_id = threadIdx.x / NPRIM, prim = threadIdx.x - cam_id * NPRIM;
+    if (tl < 2 * NPRIM && live) {
+        const int cam_id = tl / NPRIM, prim = tl - cam_id * NPRIM;
         build_prim(cam_id ? top : front, cam_id, W, H, S, prim);
     }
     __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (!live) return;
     const size_t img_bytes = (size_t)H * W * 3;
-    unsigned char *st = stage[wave];
-    // waves 0,1 render camera_front (even / odd bands), waves 2,3 camera_top: everything camera-dependent is wave-uniform
-    const int cam = wave >> 1;
+    unsigned char *st = FIXED ? stage_fixed + wave * (12 * TW) : stage_dyn + wave * (4 * RB);
+    const int marker = __builtin_amdgcn_readfirstlane(S.marker);
+    // co-resident workgroups start at different bands (hashed phase) so that their ray-cast (VALU-bound) and copy
+    // (memory-bound) stretches overlap instead of all waves of a SIMD hitting the arm's rows together
+    const int NB = H / 4;
+    const int rot = (int)(((unsigned)env * 0x9E3779B1u) >> 29) * (2 * NB / 15);   // eight phases, 0 .. 7 (2 NB / 15) < NB  (NB = 60: steps of 8 bands)
+    const int tx = lane & 15, ty = lane >> 4;   // pixel of this lane inside a 16 x 4 tile
+    // four waves per env: waves 0,1 render camera_front (even / odd bands), waves 2,3 camera_top; two: one camera each; one: both cameras in turn.
+    // Everything camera-dependent is wave-uniform
+    constexpr int CAM_STEP = WPE >= 2 ? 2 : 1, BAND_STEP = WPE == 4 ? 2 : 1;
+    int cam = WPE == 4 ? wsub >> 1 : (WPE == 2 ? wsub : 0);
+    do {
     const LcrCam &C = cam ? top : front;
     const f3 ro = mk(C.px, C.py, C.pz), CX = mk(C.xx, C.xy, C.xz), CY = mk(C.yx, C.yy, C.yz), CZ = mk(C.zx, C.zy, C.zz);
-    const int marker = __builtin_amdgcn_readfirstlane(S.marker);
     // culling: one primitive per lane (lane k <-> primitive k).  Per band, every lane computes the pixel interval [xa, xb] its primitive can cover on the
     // band's 4 rows (arm boxes: 2D stadium silhouette, the other boxes: bounding box) -> the interval [ta, tb] of 16-pixel tile columns it touches.
     const float *cull = S.cull[cam][lane < NPRIM ? lane : 0];
-    const u32x4 *bg = reinterpret_cast<const u32x4 *>(P.img_bg) + (size_t)cam * H * 60;
+    const u32x4 *bg = reinterpret_cast<const u32x4 *>(P.img_bg) + (size_t)cam * NB * VB;
     u32x4 *out = reinterpret_cast<u32x4 *>((cam ? P.img_top : P.img_front) + (size_t)env * img_bytes);
-    const bool l3 = lane < 48;               // a band = 240 vectors = 3 full wave loads + 48 lanes
-    const int lq = l3 ? lane : 47;
-    // co-resident workgroups start at different bands (hashed phase) so that their ray-cast (VALU-bound) and copy
-    // (memory-bound) stretches overlap instead of all waves of a SIMD hitting the arm's rows together
-    constexpr int NB = H / 4;
-    const int rot = (int)((blockIdx.x * 0x9E3779B1u) >> 29) * 8;
-    const int tx = lane & 15, ty = lane >> 4;   // pixel of this lane inside a 16 x 4 tile
-    for (int it = wave & 1; it < NB; it += 2) {
+    for (int it = WPE == 4 ? wsub & 1 : 0; it < NB; it += BAND_STEP) {
         const int b = it + rot >= NB ? it + rot - NB : it + rot;
-        u32x4 *dst = out + b * 240;
-        const u32x4 *src = bg + b * 240;
-        const u32x4 v0 = src[lane], v1 = src[64 + lane], v2 = src[128 + lane], v3 = src[192 + lq];   // in flight while the band is culled
+        u32x4 *dst = out + b * VB;
+        const u32x4 *src = bg + b * VB;
+        // a band = VB vectors = NV wave loads, the last one partial (320 wide: 240 = 3 full ones + 48 lanes); in flight while the band is culled
+        u32x4 v[NV];
+#pragma unroll
+        for (int j = 0; j < NV; j++) v[j] = src[min(64 * j + lane, VB - 1)];
         const int row0 = 4 * b;
         const f32x4 cb = *reinterpret_cast<const f32x4 *>(cull);   // y0 y1 x0 x1
         // (the base alone does not make a band worth ray-casting: it is in the background already)
@@ -362,27 +397,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         unsigned U = 0u;
         if (__any(ta <= tb && lane != BASE)) U = or_row0(ta <= tb && lane != BASE ? (2u << tb) - (1u << ta) : 0u);
         if (U == 0u) {
-            __builtin_nontemporal_store(v0, dst + lane);
-            __builtin_nontemporal_store(v1, dst + 64 + lane);
-            __builtin_nontemporal_store(v2, dst + 128 + lane);
-            if (l3) __builtin_nontemporal_store(v3, dst + 192 + lane);
+#pragma unroll
+            for (int j = 0; j < NV; j++)
+                if (64 * j + lane < VB) __builtin_nontemporal_store(v[j], dst + 64 * j + lane);
             continue;
         }
         u32x4 *sv = reinterpret_cast<u32x4 *>(st);
-        sv[lane] = v0; sv[64 + lane] = v1; sv[128 + lane] = v2;
-        if (l3) sv[192 + lane] = v3;
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (64 * j + lane < VB) sv[64 * j + lane] = v[j];
         // rays of this lane's tile row: d(px) = -Z + sy Y + sx(px) X, camera looks along -Z
         const float sy = -((float)(row0 + ty) + 0.5f - 0.5f * H) * C.s;
         const f3 rbase = axpy(sy, CY, neg(CZ));
         for (; U; U &= U - 1u) {
             const int t = __builtin_ctz(U);
             const unsigned m = (unsigned)__ballot(ta <= t && tb >= t);
-            const int px = 16 * t + tx;
+            // (a partial last tile column: lanes beyond the row's end follow the wave with the row's last pixel and write nothing)
+            const int pxt = 16 * t + tx, px = FIXED ? pxt : min(pxt, W - 1);
             const float sx = ((float)px + 0.5f - 0.5f * W) * C.s;
             const f3 rdu = axpy(sx, CX, rbase);
-            unsigned char *stpx = st + ty * 960 + 3 * px;
+            unsigned char *stpx = st + ty * RB + 3 * px;
             unsigned rgb = 0u;
-            const bool wrote = shade_span(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb);
+            const bool wrote = shade_span(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb) && (FIXED || pxt < W);
             if (wrote) {
                 stpx[0] = (unsigned char)rgb;
                 stpx[1] = (unsigned char)(rgb >> 8);
@@ -393,13 +429,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
                 if (lane == 0) { atomicAdd(&P.active_count[env], 1u); atomicAdd(&P.choice[env], (unsigned)__popc(m)); atomicAdd(&P.max_sweeps[env], (unsigned)nw); }
             }
         }
-        __builtin_nontemporal_store(sv[lane], dst + lane);
-        __builtin_nontemporal_store(sv[64 + lane], dst + 64 + lane);
-        __builtin_nontemporal_store(sv[128 + lane], dst + 128 + lane);
-        if (l3) __builtin_nontemporal_store(sv[192 + lane], dst + 192 + lane);
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (64 * j + lane < VB) __builtin_nontemporal_store(sv[64 * j + lane], dst + 64 * j + lane);
     }
+    } while ((cam += CAM_STEP) < 2);
 }
 
+#if LCR_RENDER_PART != 1
 // one env, arbitrary camera / resolution (render(), 640x640 camera_vizu): one thread per pixel, no culling, no cached background
 __global__ __launch_bounds__(256) void lcr_render_single_kernel(LcrDev P, LcrCam cam, int env, int W, int H, unsigned char *out) {
     __shared__ Scene S;
@@ -436,26 +473,72 @@ __global__ __launch_bounds__(256) void lcr_gather_terminal_kernel(LcrDev P, cons
     for (int j = 0; j < 3; j++) target_out[j * C + i] = P.has_target ? t[(15 + j) * N] : 0.f;
 }
 
+#endif
+
 }  // namespace
 
+// the launchers of the run-time sizes live in unit 1
+void lcr_launch_render_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, bool count, void *stream);
+
+namespace {
+template <bool COUNT, int NV, int EPW, int TW, int TH>
+void launch_obs(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream) {
+    const size_t lds = TW ? 0 : (size_t)4 * 12 * P.img_w;
+    hipLaunchKernelGGL((lcr_render_obs_kernel<COUNT, NV, EPW, TW, TH>), dim3((P.n + EPW - 1) / EPW), dim3(256), lds, (hipStream_t)stream, P, front, top);
+}
+#if LCR_RENDER_PART != 0
+template <bool COUNT>
+void launch_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream) {
+    const int W = P.img_w, epw = P.img_epw;
+    const int nv = (3 * W / 4 + 63) / 64;   // wave loads of a band: 1 up to 85 px wide, 2 up to 170, 4 up to 341, 6 up to 512
+    if (nv > 4) return launch_obs<COUNT, 6, 1, 0, 0>(P, front, top, stream);
+    if (nv > 2) return launch_obs<COUNT, 4, 1, 0, 0>(P, front, top, stream);
+    if (nv > 1) {
+        if (epw == 4) return launch_obs<COUNT, 2, 4, 0, 0>(P, front, top, stream);
+        if (epw == 2) return launch_obs<COUNT, 2, 2, 0, 0>(P, front, top, stream);
+        return launch_obs<COUNT, 2, 1, 0, 0>(P, front, top, stream);
+    }
+    if (epw == 4) return launch_obs<COUNT, 1, 4, 0, 0>(P, front, top, stream);
+    if (epw == 2) return launch_obs<COUNT, 1, 2, 0, 0>(P, front, top, stream);
+    return launch_obs<COUNT, 1, 1, 0, 0>(P, front, top, stream);
+}
+#endif
+}  // namespace
+
+#if LCR_RENDER_PART != 0
+void lcr_launch_render_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, bool count, void *stream) {
+    if (count) launch_obs_sized<true>(P, front, top, stream);
+    else launch_obs_sized<false>(P, front, top, stream);
+}
+#endif
+
+#if LCR_RENDER_PART != 1
 int lcr_launch_gather_terminal(const LcrDev &P, const int *ids_dev, int count, float *qpos_out, float *target_out, void *stream) {
     hipLaunchKernelGGL(lcr_gather_terminal_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, ids_dev, count, qpos_out, target_out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// Envs per workgroup of the frame kernel, from the frame size alone (profiles/frame_sizes.txt: four envs per workgroup take 0.461 instead of 0.499 ms at
+// 64 x 64 and 0.587 instead of 0.624 at 84 x 84, 32 768 envs; at 128 x 128 the mappings measure the same, 0.97-0.98 ms; larger frames were not measured and keep one)
+int lcr_render_envs_per_workgroup(int W, int H) {
+    if (W > 170) return 1;   // (the several-envs builds exist for NV <= 2 only)
+    return W * H <= 128 * 128 ? 4 : 1;
+}
+
 int lcr_launch_render_obs(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream) {
     if (!P.img_front || !P.img_top) return 0;
     static const int count = [] { const char *e = getenv("LCR_RENDER_COUNT"); return e ? atoi(e) : 0; }();   // diagnostics: tools/render_work.py
-    if (count) hipLaunchKernelGGL(lcr_render_obs_kernel<true>, dim3(P.n), dim3(256), 0, (hipStream_t)stream, P, front, top);
-    else hipLaunchKernelGGL(lcr_render_obs_kernel<false>, dim3(P.n), dim3(256), 0, (hipStream_t)stream, P, front, top);
+    if (P.img_w != 320 || P.img_h != 240) lcr_launch_render_obs_sized(P, front, top, count != 0, stream);
+    else if (count) launch_obs<true, 4, 1, 320, 240>(P, front, top, stream);
+    else launch_obs<false, 4, 1, 320, 240>(P, front, top, stream);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
 int lcr_launch_render_bg(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream) {
     if (!P.img_bg) return 0;
-    hipLaunchKernelGGL(lcr_render_bg_kernel, dim3((2 * 320 * 240 + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, front, top);
+    hipLaunchKernelGGL(lcr_render_bg_kernel, dim3((2 * P.img_w * P.img_h + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, front, top);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
@@ -465,3 +548,4 @@ int lcr_launch_render_single(const LcrDev &P, const LcrCam &cam, int env, int W,
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
+#endif

@@ -2,8 +2,8 @@
 (gym_lowcostrobot/envs/wrappers/record_hdf5.py:52-61,111):
 
     one file per episode  "{name_prefix}-episode-{id}.hdf5"  with datasets
-        observations/images/front   (T, 240, 320, 3) uint8      <- obs["image_front"]
-        observations/images/top     (T, 240, 320, 3) uint8      <- obs["image_top"]
+        observations/images/front   (T, H, W, 3) uint8          <- obs["image_front"]   (H x W: 240 x 320 unless the env was given an image_size)
+        observations/images/top     (T, H, W, 3) uint8          <- obs["image_top"]
         observations/qpos           (T, 6) float32               <- obs["arm_qpos"]
         observations/qvel           (T, 6) float32               <- obs["arm_qvel"]
         action                      (T, k) float32
@@ -166,7 +166,7 @@ class VecRecorder:
 
     def after_step(self, actions):
         """actions: (N, k) host array that was just applied.  Only the recorded envs' data crosses PCIe: one packed copy of the
-        state outputs (132 B/env) and one 230 400-B copy per recorded env and camera."""
+        state outputs (132 B/env) and one frame-sized copy (230 400 B at 240 x 320) per recorded env and camera."""
         sim = self.sim
         h = sim.fetch_host()
         has_img = sim.image_front is not None
@@ -188,8 +188,9 @@ class VecRecorder:
                     if sim.task_name == "stack":
                         qpos[13:16] = t[15:18]; qpos[16:20] = tq[4:8, e]
                     tgt = t[15:18] if sim.task_name in ("push", "pick_place") else None
-                    o["image_front"] = sim.render_state(qpos, tgt, "camera_front")
-                    o["image_top"] = sim.render_state(qpos, tgt, "camera_top")
+                    ih, iw = sim.image_size
+                    o["image_front"] = sim.render_state(qpos, tgt, "camera_front", iw, ih)
+                    o["image_top"] = sim.render_state(qpos, tgt, "camera_top", iw, ih)
             else:
                 o = {"arm_qpos": h["arm_qpos"][e].copy(), "arm_qvel": h["arm_qvel"][e].copy()}
                 if has_img:

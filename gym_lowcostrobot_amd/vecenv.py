@@ -51,8 +51,8 @@ def _obs_spaces(sim, observation_mode):
     if sim.task_name in ("push", "pick_place"):
         subs["target_pos"] = sp.Box(-10.0, 10.0, shape=(3,), dtype=np.float32)     # always present (push_cube_env.py:297)
     if observation_mode in ("image", "both"):
-        subs["image_front"] = sp.Box(0, 255, shape=(240, 320, 3), dtype=np.uint8)
-        subs["image_top"] = sp.Box(0, 255, shape=(240, 320, 3), dtype=np.uint8)
+        subs["image_front"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)   # (240, 320, 3) unless VecSim was given an image_size
+        subs["image_top"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)
     if observation_mode in ("state", "both"):
         subs[sim.cube_name] = sp.Box(-10.0, 10.0, shape=(3,), dtype=np.float32)
         if sim.task_name == "stack":
@@ -265,8 +265,8 @@ class LowCostRobotVectorEnv:
                     fin["cube_blue_pos"] = t[:, 15:18].copy()
             if v.observation_mode in ("image", "both"):   # final frames: ONE batched ray-cast of the terminal poses of the envs that were reset
                 ridx = np.nonzero(h["did_reset"])[0]
-                fin["image_front"] = np.zeros((self.num_envs, 240, 320, 3), np.uint8)   # (calloc'ed: pages of envs that were not reset are never touched)
-                fin["image_top"] = np.zeros((self.num_envs, 240, 320, 3), np.uint8)
+                fin["image_front"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)   # (calloc'ed: pages of envs that were not reset are never touched)
+                fin["image_top"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)
                 if ridx.size:
                     fin["image_front"][ridx], fin["image_top"][ridx] = sim.render_terminal(ridx)
             fin = {k: fin[k] for k in v._keys}

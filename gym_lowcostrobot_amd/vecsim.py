@@ -85,6 +85,7 @@ class VecSim:
         ls_tol=None,
         finger_floor_condim=None,
         coop_share=None,
+        image_size=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -155,6 +156,12 @@ class VecSim:
         if coop_share not in _capi.COOP_SHARE:   # one-cube Newton kernel: who solves a wave's coupled envs (None = shared; "owner" | "handoff": A/B runs, bit-identical)
             raise ValueError(f"invalid coop_share {coop_share!r} (None | 'owner' | 'shared' | 'handoff')")
         cfg.coop_share = _capi.COOP_SHARE[coop_share]
+        if image_size is not None:   # (height, width) of the image observations, numpy order as the arrays are (N, H, W, 3); None = 240 x 320.  The library checks the values
+            try:
+                ih, iw = (int(v) for v in image_size)
+            except (TypeError, ValueError):
+                raise ValueError(f"image_size must be None or (height, width), got {image_size!r}") from None
+            cfg.image_height, cfg.image_width = ih, iw
         self.cfg = cfg
         self.n = int(n_envs)
         self.device = int(device)
@@ -179,7 +186,8 @@ class VecSim:
         self.arm_qvel = DeviceArray(self, ov.arm_qvel, (6, N), np.float32)
         self.cube_pos = DeviceArray(self, ov.cube_pos, (3, N), np.float32)
         self.aux_pos = DeviceArray(self, ov.aux_pos, (3, N), np.float32) if ov.has_aux else None
-        img = (N, _capi.IMG_H, _capi.IMG_W, 3)
+        self.image_size = (int(ov.image_height), int(ov.image_width)) if ov.image_front else (int(cfg.image_height) or _capi.IMG_H, int(cfg.image_width) or _capi.IMG_W)
+        img = (N,) + self.image_size + (3,)
         self.image_front = DeviceArray(self, ov.image_front, img, np.uint8) if ov.image_front else None
         self.image_top = DeviceArray(self, ov.image_top, img, np.uint8) if ov.image_top else None
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
@@ -272,11 +280,11 @@ class VecSim:
 
     def render_terminal(self, env_ids):
         """last frames (camera_front, camera_top) of the episodes the last step ended in the listed envs, ray-cast as ONE batch from their
-        terminal poses (the envs themselves have already been reset): two (len(env_ids), 240, 320, 3) uint8 arrays"""
+        terminal poses (the envs themselves have already been reset): two (len(env_ids), H, W, 3) uint8 arrays, (H, W) = self.image_size"""
         ids = np.ascontiguousarray(env_ids, np.int32)
         if ids.size and self.image_front is not None and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():   # (lcr.h: the terminal poses belong to envs the LAST step reset; anything else is a stale frame)
             raise ValueError("render_terminal: every listed env must have finished an episode in the last step (did_reset)")
-        front = np.empty((ids.size, _capi.IMG_H, _capi.IMG_W, 3), np.uint8)
+        front = np.empty((ids.size,) + self.image_size + (3,), np.uint8)
         top = np.empty_like(front)
         check(self.L.lcr_render_terminal(self.handle, _vp(ids), int(ids.size), _vp(front), _vp(top)))
         return front, top

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LCR_ABI_VERSION 6
+#define LCR_ABI_VERSION 7
 
 typedef enum lcr_status {
     LCR_OK = 0,
@@ -58,6 +58,7 @@ enum {
                                                  reference never resets it); lcr_reset / auto-reset / lcr_set_state clear them */
 };
 
+/* the default size of the image observations (the reference's, reach_cube_env.py:288-292): lcr_config.image_width = image_height = 0 */
 #define LCR_IMG_H 240
 #define LCR_IMG_W 320
 
@@ -139,6 +140,12 @@ typedef struct lcr_config {
                                   four waves per workgroup; a wave stages its coupled envs into a queue in LDS before its small solves, and 2 = shared (0 = default): any wave of the
                                   workgroup claims them, the owner its own first, and a wave that has finished its step keeps serving the queue; 1 = owner only; 3 = always hand
                                   off (another wave solves them: tests).  A/B switch only: the results are bit-identical under all three.  Other values: LCR_ERR_INVALID */
+    /* ABI v7 */
+    int32_t image_width;       /* image_width x image_height: size of the image observations (observation_mode image / both; checked whatever the mode).  0, 0 = LCR_IMG_W x LCR_IMG_H (320 x 240, the
+                                  reference's).  Otherwise each a multiple of 4 in [16, 512]: a band of 4 rows is 12 W bytes, a multiple of 16 exactly when W % 4 == 0, so every
+                                  band and every frame (3 W H bytes) stays 16-byte aligned for the frame kernel's 16-B stores; W <= 512 keeps its mask of 16-pixel tile columns
+                                  in one 32-bit word.  One zero and one non-zero, or anything else: LCR_ERR_INVALID */
+    int32_t image_height;
 } lcr_config;
 
 typedef enum lcr_solver { LCR_SOLVER_PGS = 0, LCR_SOLVER_NEWTON = 1 } lcr_solver;
@@ -164,8 +171,10 @@ typedef struct lcr_obs_view {
     const float *arm_qvel;      /* [6][N] */
     const float *cube_pos;      /* [3][N]  (stack: cube_red_pos) */
     const float *aux_pos;       /* [3][N]  or NULL */
-    const uint8_t *image_front; /* [N][240][320][3] or NULL (observation_mode image/both); approximate ray-cast, see lcr_render.hip */
-    const uint8_t *image_top;   /* [N][240][320][3] or NULL */
+    const uint8_t *image_front; /* [N][H][W][3] at the configured size, or NULL (observation_mode image/both); approximate ray-cast, see lcr_render.hip */
+    const uint8_t *image_top;   /* [N][H][W][3] or NULL */
+    int32_t image_width;        /* ABI v7: the size in use, image_width x image_height (320, 240 by default; 0, 0 without images) */
+    int32_t image_height;
 } lcr_obs_view;
 
 /* step() return values (reach_cube_env.py:313-333) + SB3 auto-reset bookkeeping */
@@ -211,6 +220,7 @@ typedef struct lcr_host_view {
  *                         StackTwoCubes and PushCubeLoop; 0 = never cooperatively)
  *   LCR_RENDER_OVERLAP=0  image observations: frames on the handle's stream after the step kernel instead of on the second stream (see lcr_step)
  *   LCR_STEP_KERNEL=single|coop1|coop2, LCR_STACK_LDS=small|big   sweep kernels (LCR_PRESET_FAST): pin a kernel family / LDS variant
+ *   LCR_RENDER_EPW=1|2|4  frame kernel, frames up to 170 px wide: envs per workgroup instead of the choice by frame size (tools/frame_sizes.py; same bytes under all three)
  *   LCR_RENDER_COUNT=1    frame kernel: count ray-cast passes into the diagnostics arrays (tools/render_work.py; read at the first frame launch) */
 int lcr_abi_version(void);
 const char *lcr_last_error(void);
@@ -245,7 +255,7 @@ int lcr_reset(lcr_sim *sim, const uint8_t *mask_host, const uint64_t *seeds_host
 
 /* == step(action) (reach_cube_env.py:313-333) for all envs: apply_action (joint or ee+IK) -> 20 physics
  * substeps -> reward / terminated / truncated -> fused auto-reset.  action_dev: [k][N] float32.
- * Asynchronous.  With image observations the two frames of every env are ray-cast on a second, internal stream from a snapshot of the poses, so that the step kernel of
+ * Asynchronous.  With image observations the two frames of every env (at the configured size) are ray-cast on a second, internal stream from a snapshot of the poses, so that the step kernel of
  * the NEXT lcr_step overlaps them (BASELINE config 5: 9.7 -> see DESIGN.md section 3.4).  Every other entry point of this API first makes the handle's stream wait for
  * those frames; a caller that reads lcr_obs_view.image_* with its own kernels on the handle's stream calls lcr_sync (or any other entry point) first.
  * LCR_RENDER_OVERLAP=0 in the environment: frames on the handle's stream, after the step kernel. */
@@ -312,7 +322,7 @@ int lcr_render_state(lcr_sim *sim, int camera, int width, int height, const doub
  * examples/gym_manipulation_sb3.py:34-39 with observation_mode image / both; reach_cube_env.py:288-292): the step kernel has already reset
  * those envs, so their frame buffers show the reset state; this draws camera_front / camera_top of the TERMINAL poses (terminal_obs +
  * terminal_quat of the last step) of the `count` listed envs with the observation ray-caster, as one batch, into
- * front_host / top_host [count][240][320][3].  Needs observation_mode image / both.  Synchronous.
+ * front_host / top_host [count][H][W][3] (the configured size).  Needs observation_mode image / both.  Synchronous.
  * PRECONDITION: every listed env was reset by the LAST lcr_step (out.did_reset[id] != 0) -- the terminal pose arrays are written only by lanes that auto-reset, an
  * env that did not finish shows the last frame of an OLDER episode (or zeros before its first reset).  The library does not re-read did_reset here; the Python
  * binding (VecSim.render_terminal) checks it and raises ValueError. */

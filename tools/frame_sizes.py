@@ -1,0 +1,65 @@
+"""Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
+    python tools/frame_sizes.py [n_envs] [task]
+For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
+  (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
+       back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
+  (ii) step + frames, closed loop (a sync after every step, what a policy that reads the frames sees) and open loop (steps enqueued back to back): env-steps/s.
+LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
+import os
+import sys
+import time
+
+sys.path.insert(0, ".")
+import numpy as np  # noqa: E402
+
+from gym_lowcostrobot_amd import VecSim  # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
+task = sys.argv[2] if len(sys.argv) > 2 else "stack"
+SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
+SOAK_S, WINDOWS, STEPS = 2.0, 7, 60
+print(f"frame sizes: {task}, {n} envs, default preset, LCR_RENDER_EPW={os.environ.get('LCR_RENDER_EPW', '(by frame size)')}")
+print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
+rows = []
+for H, W in SIZES:
+    sim = VecSim(task, n, observation_mode="both", image_size=(H, W))
+    assert sim.image_size == (H, W)
+    act = [sim.alloc_actions() for _ in range(8)]
+    for t, a in enumerate(act):
+        sim.fill_random_actions(a, 1, t)
+    for t in range(12):
+        sim.step_device(act[t % 8].ptr)
+    mask = np.zeros(n, np.uint8)
+    nbytes = 2 * H * W * 3 * n
+    sim.reset(mask=mask); sim.sync()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < SOAK_S:
+        for _ in range(20):
+            sim.reset(mask=mask)
+        sim.sync()
+    w = []
+    for _ in range(WINDOWS):
+        sim.timer_begin()
+        for _ in range(10):
+            sim.reset(mask=mask)
+        w.append(sim.timer_end() / 10)
+    ms = float(np.median(w))
+    sim.sync()
+    t0 = time.perf_counter()
+    for t in range(STEPS):
+        sim.step_device(act[t % 8].ptr)
+        sim.sync()
+    closed = n * STEPS / (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    for t in range(STEPS):
+        sim.step_device(act[t % 8].ptr)
+    sim.sync()
+    opened = n * STEPS / (time.perf_counter() - t0)
+    rows.append((H, W, ms))
+    print(f"{H:4d}x{W:<4d} {ms:16.3f} {min(w):7.3f} {max(w):7.3f} {nbytes / 1e9:11.3f} {nbytes / ms / 1e9:6.2f} {closed:20.3e} {opened:18.3e}", flush=True)
+    for a in act:
+        sim.free(a)
+    sim.close()
+base = rows[0][2]
+for H, W, ms in rows[1:]:
+    print(f"  {H}x{W}: {ms / base:.3f} of the 240x320 kernel's time for {H * W / (240 * 320):.3f} of its bytes" + ("" if ms < base else "   <-- NOT faster than 240x320"))
