@@ -26,6 +26,9 @@ COMPAT_ZERO_QVEL_ON_RESET = 1
 COMPAT_COLD_SOLVE_EACH_STEP = 2   # contact solver starts every control step from zero forces (default: forces carried across steps)
 IMG_H, IMG_W = 240, 320   # LCR_IMG_H / LCR_IMG_W: the default size of the image observations (lcr_config.image_width = image_height = 0)
 
+PLANE_DEPTH, PLANE_SEGMENTATION = 1, 2   # LCR_PLANE_*: bits of lcr_enable_image_planes
+IMAGE_PLANES = {"depth": PLANE_DEPTH, "segmentation": PLANE_SEGMENTATION}
+
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 # every symbol include/lcr.h declares (tests check the .so exports exactly these)
@@ -35,6 +38,7 @@ SYMBOLS = [
     "lcr_get_obs", "lcr_get_outputs", "lcr_fetch_host", "lcr_get_state", "lcr_set_state", "lcr_malloc", "lcr_free",
     "lcr_memcpy_h2d", "lcr_memcpy_d2h", "lcr_timer_begin", "lcr_timer_end", "lcr_fill_random_actions",
     "lcr_calibrate_copy", "lcr_render", "lcr_render_state", "lcr_render_terminal", "lcr_step_kernel_family",
+    "lcr_enable_image_planes", "lcr_get_image_planes", "lcr_render_planes", "lcr_render_state_planes", "lcr_render_terminal_planes",
 ]
 
 
@@ -92,6 +96,19 @@ class LcrObsView(ctypes.Structure):
         ("image_top", ctypes.c_void_p),
         ("image_width", ctypes.c_int32),   # ABI v7: the size in use (0, 0 without images)
         ("image_height", ctypes.c_int32),
+    ]
+
+
+class LcrPlanesView(ctypes.Structure):
+    _fields_ = [
+        ("planes", ctypes.c_uint32),       # LCR_PLANE_* bits in use (0: none, every pointer NULL)
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("depth_far", ctypes.c_float),
+        ("depth_front", ctypes.c_void_p),  # [N][H][W] float32 metres along the optical axis
+        ("depth_top", ctypes.c_void_p),
+        ("seg_front", ctypes.c_void_p),    # [N][H][W] uint8 ids
+        ("seg_top", ctypes.c_void_p),
     ]
 
 
@@ -202,6 +219,11 @@ def load():
     L.lcr_render.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.lcr_render_state.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
     L.lcr_render_terminal.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    L.lcr_enable_image_planes.argtypes = [vp, ctypes.c_uint32, ctypes.c_float]
+    L.lcr_get_image_planes.argtypes = [vp, ctypes.POINTER(LcrPlanesView)]
+    L.lcr_render_planes.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    L.lcr_render_state_planes.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    L.lcr_render_terminal_planes.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

@@ -35,6 +35,8 @@ ITER_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          # the frame kernels: the default 320 x 240 build (+ background, single-frame and gather kernels) and the builds for run-time sizes, a code object each (lcr_render.hip)
          ("lcr_render.hip", "lcr_render.o", ["-DLCR_RENDER_PART=0"]), ("lcr_render.hip", "lcr_render_sizes.o", ["-DLCR_RENDER_PART=1"]),
+         # the frame kernels that also draw the depth / segmentation planes (run-time sizes only), their background and single-frame kernels
+         ("lcr_render.hip", "lcr_render_planes.o", ["-DLCR_RENDER_PART=3"]),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),

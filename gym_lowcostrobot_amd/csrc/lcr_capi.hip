@@ -98,7 +98,17 @@ struct lcr_sim {
     bool snap_used[2];
     int rpar, rlast;
     bool rpending;
+    // depth / segmentation planes of the frames (lcr_enable_image_planes): one allocation, fixed for the life of the handle
+    uint32_t planes;             // LCR_PLANE_* bits in use, 0: none
+    LcrPlanes pl;
+    void *planes_mem;
 };
+
+// whatever draws the handle's colour frames draws its enabled planes in the same launch
+static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream) {
+    if (s->planes) return lcr_launch_render_obs_planes(P, s->cam_front, s->cam_top, s->pl, stream);
+    return lcr_launch_render_obs(P, s->cam_front, s->cam_top, stream);
+}
 
 static int join_render(lcr_sim *s) {
     if (s->rpending) {
@@ -512,6 +522,7 @@ void lcr_destroy(lcr_sim *s) {
     (void)hipEventDestroy(s->ev1);
     if (s->render_dev) (void)hipFree(s->render_dev);
     if (s->term_stage) (void)hipFree(s->term_stage);
+    if (s->planes_mem) (void)hipFree(s->planes_mem);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
     delete s;
@@ -550,7 +561,7 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
     int rc = lcr_launch_reset(s->dev, mask_host ? s->mask_dev : nullptr, seeds_host ? s->seeds_dev : nullptr, 0, 0, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "reset kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     if (s->has_images) {
-        rc = lcr_launch_render_obs(s->dev, s->cam_front, s->cam_top, s->stream);
+        rc = launch_frames(s, s->dev, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
     // the staging copies above read caller memory: do not return before they are consumed
@@ -575,12 +586,12 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         HIPCHK(hipStreamWaitEvent(s->rstream, s->ev_snap[p], 0));
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
-        rc = lcr_launch_render_obs(R, s->cam_front, s->cam_top, s->rstream);
+        rc = launch_frames(s, R, s->rstream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
     } else if (s->has_images) {
-        rc = lcr_launch_render_obs(s->dev, s->cam_front, s->cam_top, s->stream);
+        rc = launch_frames(s, s->dev, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
     return LCR_OK;
@@ -860,6 +871,191 @@ int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         HIPCHK(hipMemcpyAsync(front_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipMemcpyAsync(top_host + (size_t)done * img, base + o_tp, img * c, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    return LCR_OK;
+}
+
+// ---- depth / segmentation planes of the image observations ----
+
+static int ensure_render_scratch(lcr_sim *s, size_t need) {
+    if (need <= s->render_bytes) return LCR_OK;
+    if (s->render_dev) (void)hipFree(s->render_dev);
+    s->render_dev = nullptr; s->render_bytes = 0;
+    hipError_t e = hipMalloc((void **)&s->render_dev, need);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+    s->render_bytes = need;
+    return LCR_OK;
+}
+
+int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (planes == 0 || (planes & ~(uint32_t)(LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION)))
+        return fail(LCR_ERR_INVALID, "planes must be LCR_PLANE_DEPTH (1), LCR_PLANE_SEGMENTATION (2) or both (3), got %u", planes);
+    uint32_t bits;
+    memcpy(&bits, &depth_far, sizeof bits);   // (this file is compiled with -ffast-math: NaN and infinity are told by their exponent bits)
+    if ((bits & 0x7f800000u) == 0x7f800000u) return fail(LCR_ERR_INVALID, "depth_far must be finite, in (0, 1000] metres");
+    if (depth_far <= 0.f || depth_far > 1000.f) return fail(LCR_ERR_INVALID, "depth_far must lie in (0, 1000] metres, got %g", (double)depth_far);
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to add planes to");
+    if (s->planes) {
+        if (s->planes == planes && s->pl.far == depth_far) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "planes %u with depth_far %g are enabled already and fixed for the life of the handle (asked for planes %u, depth_far %g)", s->planes,
+                    (double)s->pl.far, planes, (double)depth_far);
+    }
+    const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool dep = planes & LCR_PLANE_DEPTH, seg = planes & LCR_PLANE_SEGMENTATION;
+    size_t off = 0;
+    const size_t o_bgd = off; off += al(2 * px * sizeof(float));
+    const size_t o_bgs = off; off += al(2 * px);
+    const size_t o_d0 = off; if (dep) off += al(N * px * sizeof(float));
+    const size_t o_d1 = off; if (dep) off += al(N * px * sizeof(float));
+    const size_t o_s0 = off; if (seg) off += al(N * px);
+    const size_t o_s1 = off; if (seg) off += al(N * px);
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the image planes failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    LcrPlanes PL{};
+    PL.bg_depth = (float *)(base + o_bgd);
+    PL.bg_seg = (unsigned char *)(base + o_bgs);
+    PL.depth_front = dep ? (float *)(base + o_d0) : nullptr;
+    PL.depth_top = dep ? (float *)(base + o_d1) : nullptr;
+    PL.seg_front = seg ? (unsigned char *)(base + o_s0) : nullptr;
+    PL.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
+    PL.far = depth_far;
+    // the background planes, then colours and planes of the current state
+    int rc = lcr_launch_render_bg_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
+    if (!rc) rc = lcr_launch_render_obs_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "drawing the image planes failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->pl = PL;
+    s->planes_mem = mem;
+    s->planes = planes;
+    return LCR_OK;
+}
+
+int lcr_get_image_planes(lcr_sim *s, lcr_planes_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the planes are drawn with the frames, on the second stream after a step: the handle's stream waits for them here)
+    memset(out, 0, sizeof *out);
+    if (!s->planes) return LCR_OK;
+    out->planes = s->planes;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->depth_far = s->pl.far;
+    out->depth_front = s->pl.depth_front;
+    out->depth_top = s->pl.depth_top;
+    out->seg_front = s->pl.seg_front;
+    out->seg_top = s->pl.seg_top;
+    return LCR_OK;
+}
+
+// one frame's planes of the pose arrays of `P` (env `env`), drawn into the scratch frame and copied to the host
+static int render_planes_of(lcr_sim *s, const LcrDev &P, int env, int camera, int width, int height, size_t o_seg, float *depth_host, uint8_t *seg_host) {
+    LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
+    cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
+    const size_t px = (size_t)width * height;
+    const float far = s->planes ? s->pl.far : 10.f;
+    int rc = lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_host ? (float *)s->render_dev : nullptr, seg_host ? s->render_dev + o_seg : nullptr, s->stream);
+    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (depth_host) HIPCHK(hipMemcpy(depth_host, s->render_dev, px * sizeof(float), hipMemcpyDeviceToHost));
+    if (seg_host) HIPCHK(hipMemcpy(seg_host, s->render_dev + o_seg, px, hipMemcpyDeviceToHost));
+    return LCR_OK;
+}
+
+int lcr_render_planes(lcr_sim *s, int env, int camera, int width, int height, float *depth_host, uint8_t *seg_host) {
+    SIMCHK(s);
+    if (!depth_host && !seg_host) return fail(LCR_ERR_INVALID, "depth_host and seg_host are both NULL");
+    if (env < 0 || env >= s->dev.n) return fail(LCR_ERR_INVALID, "env %d out of range", env);
+    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
+    const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255;
+    if (int rc = ensure_render_scratch(s, o_seg + px)) return rc;
+    return render_planes_of(s, s->dev, env, camera, width, height, o_seg, depth_host, seg_host);
+}
+
+int lcr_render_state_planes(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, float *depth_host, uint8_t *seg_host) {
+    SIMCHK(s);
+    if (!qpos_host || (!depth_host && !seg_host)) return fail(LCR_ERR_INVALID, "NULL argument");
+    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
+    const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255, o_pose = (o_seg + px + 255) & ~(size_t)255;
+    if (int rc = ensure_render_scratch(s, o_pose + 256)) return rc;
+    // a one-env view of the handle whose state arrays are the caller's pose, staged behind the planes
+    float st[32];
+    for (int i = 0; i < s->nq; i++) st[i] = (float)qpos_host[i];
+    for (int i = 0; i < 3; i++) st[s->nq + i] = target_host ? target_host[i] : 0.f;
+    float *stage = (float *)(s->render_dev + o_pose);
+    HIPCHK(hipMemcpyAsync(stage, st, sizeof(float) * (s->nq + 3), hipMemcpyHostToDevice, s->stream));
+    LcrDev P1 = s->dev;
+    P1.n = 1;
+    P1.qpos = stage;
+    P1.target = stage + s->nq;
+    return render_planes_of(s, P1, 0, camera, width, height, o_seg, depth_host, seg_host);
+}
+
+int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int count, float *depth_front, float *depth_top, uint8_t *seg_front, uint8_t *seg_top) {
+    SIMCHK(s);
+    if (!s->planes) return fail(LCR_ERR_INVALID, "no image planes are enabled on this sim (lcr_enable_image_planes)");
+    const bool dep = s->planes & LCR_PLANE_DEPTH, seg = s->planes & LCR_PLANE_SEGMENTATION;
+    if (count < 0 || (count > 0 && (!env_ids_host || (dep && (!depth_front || !depth_top)) || (seg && (!seg_front || !seg_top)))))
+        return fail(LCR_ERR_INVALID, "NULL argument (only the pointers of a plane that is not enabled may be NULL)");
+    for (int i = 0; i < count; i++)
+        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
+    // the frame kernel draws the colours in the same launch: they are staged too and dropped
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, per_env = 2 * (img + (dep ? px * sizeof(float) : 0) + (seg ? px : 0));
+    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass, as lcr_render_terminal
+    const size_t chunk = BUDGET / per_env;
+    const int cap = (size_t)count < chunk ? count : (int)chunk;
+    if (cap == 0) return LCR_OK;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    const size_t o_ids = off; off += al(sizeof(int) * cap);
+    const size_t o_q = off; off += al(sizeof(float) * s->nq * cap);
+    const size_t o_t = off; off += al(sizeof(float) * 3 * cap);
+    const size_t o_f = off; off += al(img * cap);
+    const size_t o_tp = off; off += al(img * cap);
+    const size_t o_d0 = off; if (dep) off += al(px * sizeof(float) * cap);
+    const size_t o_d1 = off; if (dep) off += al(px * sizeof(float) * cap);
+    const size_t o_s0 = off; if (seg) off += al(px * cap);
+    const size_t o_s1 = off; if (seg) off += al(px * cap);
+    if (off > s->term_stage_bytes) {
+        if (s->term_stage) (void)hipFree(s->term_stage);
+        s->term_stage = nullptr; s->term_stage_bytes = 0;
+        hipError_t e = hipMalloc((void **)&s->term_stage, off);
+        if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+        s->term_stage_bytes = off;
+    }
+    char *base = (char *)s->term_stage;
+    for (int done = 0; done < count; done += cap) {
+        const int c = count - done < cap ? count - done : cap;
+        HIPCHK(hipMemcpyAsync(base + o_ids, env_ids_host + done, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
+        int rc = lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+        LcrDev P1 = s->dev;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
+        P1.n = c;
+        P1.qpos = (float *)(base + o_q);
+        P1.target = (float *)(base + o_t);
+        P1.img_front = (unsigned char *)(base + o_f);
+        P1.img_top = (unsigned char *)(base + o_tp);
+        LcrPlanes PL1 = s->pl;
+        PL1.depth_front = dep ? (float *)(base + o_d0) : nullptr;
+        PL1.depth_top = dep ? (float *)(base + o_d1) : nullptr;
+        PL1.seg_front = seg ? (unsigned char *)(base + o_s0) : nullptr;
+        PL1.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
+        rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (dep) {
+            HIPCHK(hipMemcpyAsync(depth_front + (size_t)done * px, base + o_d0, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(depth_top + (size_t)done * px, base + o_d1, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
+        }
+        if (seg) {
+            HIPCHK(hipMemcpyAsync(seg_front + (size_t)done * px, base + o_s0, px * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(seg_top + (size_t)done * px, base + o_s1, px * c, hipMemcpyDeviceToHost, s->stream));
+        }
         HIPCHK(hipStreamSynchronize(s->stream));
     }
     return LCR_OK;

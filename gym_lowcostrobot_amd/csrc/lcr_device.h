@@ -85,6 +85,15 @@ struct LcrCam {
     float s;
 };
 
+// depth / segmentation planes of the image observations (lcr_enable_image_planes).  A kernel argument of its own: LcrDev -- and with it every kernel that draws no planes -- stays as it is
+struct LcrPlanes {
+    float *depth_front, *depth_top;        // [n][img_h][img_w] metres along the optical axis, clipped at `far`; null: plane not enabled
+    unsigned char *seg_front, *seg_top;    // [n][img_h][img_w] ids (include/lcr.h); null: plane not enabled
+    float *bg_depth;                       // [2][img_h][img_w] env-independent background (floor, sky, the arm's base) of camera_front / camera_top: what img_bg is for the colours
+    unsigned char *bg_seg;                 // [2][img_h][img_w]
+    float far;
+};
+
 // launchers implemented in lcr_kernels.hip / lcr_render.hip (plain C++ linkage, same shared object)
 int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
 // the Newton kernels of the faithful preset (lcr_kernels.hip, unit LCR_PART = 4)
@@ -104,4 +113,8 @@ int lcr_render_envs_per_workgroup(int W, int H);   // the frame kernel's mapping
 int lcr_launch_gather_terminal(const LcrDev &P, const int *ids_dev, int count, float *qpos_out, float *target_out, void *stream);
 int lcr_launch_render_bg(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream);
 int lcr_launch_render_single(const LcrDev &P, const LcrCam &cam, int env, int W, int H, unsigned char *out_dev, void *stream);
+// the planes (lcr_render.hip, unit LCR_RENDER_PART = 3): colour frames + enabled planes in one launch / their cached background / one env, one ray per pixel
+int lcr_launch_render_obs_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream);
+int lcr_launch_render_bg_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream);
+int lcr_launch_render_single_planes(const LcrDev &P, const LcrCam &cam, int env, int W, int H, float far, float *depth_dev, unsigned char *seg_dev, void *stream);
 int lcr_launch_calib_copy(const float *src, float *dst, size_t n, void *stream);

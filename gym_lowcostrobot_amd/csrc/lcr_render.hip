@@ -22,11 +22,14 @@
 
 using namespace lcrdev;
 
-// This file is compiled as two units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes; undefined =
-// everything in one unit (the tools that compile this file on its own)
+// This file is compiled as three units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes, 3 = the
+// kernels that draw the depth / segmentation planes (include/lcr.h: lcr_enable_image_planes); undefined = everything in one unit (the tools that compile this file on its own)
 #ifndef LCR_RENDER_PART
 #define LCR_RENDER_PART 2
 #endif
+#define LCR_RENDER_SMALL (LCR_RENDER_PART == 0 || LCR_RENDER_PART == 2)
+#define LCR_RENDER_SIZED (LCR_RENDER_PART == 1 || LCR_RENDER_PART == 2)
+#define LCR_RENDER_PLANES (LCR_RENDER_PART == 3 || LCR_RENDER_PART == 2)
 
 namespace {
 
@@ -195,7 +198,7 @@ DEV bool box_hit(const float *c, float sx, float sy, float tlimit, float &tmin, 
     return tmin <= tmax && tmin > 0.f && tmin < tlimit;
 }
 
-#if LCR_RENDER_PART != 1   // (the per-pixel shading of the background and single-frame kernels)
+#if LCR_RENDER_SMALL   // (the per-pixel shading of the background and single-frame kernels)
 DEV f3 floor_or_sky(f3 ro, f3 d, float inv_len, float &tfloor) {
     // checker floor below the horizon (builtin checker, 0.1 m squares; its normal is +z so the Lambert term is -d_z / |d|), gradient sky above (unshaded)
     const float rdz = d.z * inv_len;
@@ -233,8 +236,11 @@ DEV f3 shade_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, int
 
 // One tile of an observation band: ray-cast the boxes of mask `m` (wave-uniform).  The staged rows already hold the background (floor, sky, base), so a
 // lane only reports a colour when its ray hits something else.  `stpx` = this pixel's 3 staged background bytes (read for the translucent target marker
-// only).  Returns true and sets rgb when the pixel has to be rewritten.
-DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float sy, f3 d, unsigned m, const unsigned char *stpx, unsigned &rgb) {
+// only).  Returns true and sets rgb when the pixel has to be rewritten.  PLANES: the nearest opaque surface among the floor and the boxes of `m` is reported as well --
+// tnear its ray parameter (1e30: sky), knear its box (-1: floor or sky), mhit whether the translucent marker lies in front of it -- whatever the return value.
+template <bool PLANES>
+DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float sy, f3 d, unsigned m, const unsigned char *stpx, unsigned &rgb, float &tnear, int &knear,
+                    bool &mhit) {
     float tbest = d.z < -1e-6f ? -ro.z * rcp(d.z) : 1e30f;   // the floor hides what lies below it
     int kbest = -1;
     float lamd = 0.f;   // |n . d| of the nearest hit
@@ -247,6 +253,7 @@ DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float 
             else { tbest = tmin; lamd = ld; kbest = k; }
         }
     }
+    if (PLANES) { tnear = tbest; knear = kbest; mhit = talpha > 0.f; }
     const bool draw = kbest > BASE || talpha > 0.f;   // (a pixel whose nearest hit is the base keeps its background bytes)
     if (!__any(draw)) return false;
     const float inv_len = rsq(dot(d, d));
@@ -261,7 +268,7 @@ DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float 
     return draw;
 }
 
-#if LCR_RENDER_PART != 1
+#if LCR_RENDER_SMALL
 // background frames of the two observation cameras -- checker floor, sky and the arm's base: identical for every env and every step, so they
 // are rendered ONCE at lcr_create into P.img_bg ([2][H][W][3]; 460 800 B at 320 x 240, L2-resident) and copied band-wise afterwards.
 __global__ __launch_bounds__(256) void lcr_render_bg_kernel(LcrDev P, LcrCam front, LcrCam top) {
@@ -295,6 +302,10 @@ DEV unsigned or_row0(unsigned x) {
     return (unsigned)__builtin_amdgcn_readlane((int)x, 15);
 }
 
+// the optional fourth argument of the frame kernel (a parameter pack of at most one LcrPlanes)
+[[maybe_unused]] DEV LcrPlanes planes_arg() { return LcrPlanes{}; }
+[[maybe_unused]] DEV LcrPlanes planes_arg(const LcrPlanes &pl) { return pl; }
+
 // COUNT: diagnostics build (LCR_RENDER_COUNT=1 and lcr_config.diagnostics): ray-cast passes / primitive tests / pixels written per env into
 // active_count / choice / max_sweeps (tools/render_work.py)
 // Six waves per SIMD: the 80 registers that takes spill six values of the scene set-up (the chain of link frames), none in the band loop (measured, 32 768 envs:
@@ -305,8 +316,16 @@ DEV unsigned or_row0(unsigned x) {
 // 320 wide, five at 512 -- the NV = 6 build is compiled for five waves per SIMD).  NV = 16-B vectors of a band (3 W / 4 of them) a lane carries, ceil(3 W / 256).
 // EPW = envs per workgroup (1, 2, 4), the mapping for small frames: 4 / EPW waves per env -- 4: two per camera, alternate bands; 2: one per camera; 1: one wave draws
 // both frames of its env -- so that the scene set-up of EPW envs runs side by side and a workgroup lives EPW times longer against its launch.
-template <bool COUNT, int NV, int EPW, int TW, int TH>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 : 6, NV > 4 ? 5 : 6))) void lcr_render_obs_kernel(LcrDev P, LcrCam front, LcrCam top) {
+//
+// PLANES (a fourth kernel argument, LcrPlanes, is given -- `PLS` is empty or that one type, so the colour-only builds keep their signature; run-time sizes only): the enabled
+// depth / segmentation planes of PL are drawn beside the colours.  A band no silhouette touches copies the cached background bands (16 W B of depth, 4 W B of segmentation)
+// with 16-B stores.  In a touched band the segmentation band is staged in LDS behind the colours (4 W B more per wave) and leaves as 16-B stores; the depth band is NOT
+// staged -- 16 W B per wave would more than double the workgroup's LDS and leave three of the six workgroups of a CU at 320 wide -- but leaves straight from registers: the
+// ray-cast tiles store their 16 x 4 floats (64 B per row), the 16-B vectors of every other tile are copied from the background.  No byte of a plane is written twice.
+template <bool COUNT, int NV, int EPW, int TW, int TH, typename... PLS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 : 6, NV > 4 ? 5 : 6))) void lcr_render_obs_kernel(LcrDev P, LcrCam front, LcrCam top, PLS... pls) {
+    constexpr bool PLANES = sizeof...(PLS) != 0;
+    const LcrPlanes PL = planes_arg(pls...);
     // A workgroup owns EPW envs (one: 2 H rows, front frame then top frame); a wave handles one BAND of 4 rows at a time (12 W B = 3 W / 4 lanes x
     // 16 B; 3 840 B = 240 lanes at 320 wide).  The band starts as a copy of the cached background band (L2 hit); if no primitive's silhouette touches
     // it (wave-uniform) it leaves straight away as non-temporal 16-B stores.  Otherwise the band is
@@ -319,6 +338,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     constexpr bool FIXED = TW != 0;
     static_assert(!FIXED || (TW % 16 == 0 && TH % 4 == 0 && (3 * TW / 4 + 63) / 64 == NV), "a fixed size has whole tile columns and its own NV");
     static_assert(EPW == 1 || EPW == 2 || EPW == 4, "1, 2 or 4 waves per env");
+    static_assert(!PLANES || (!FIXED && !COUNT), "the planes build takes its size at run time and counts nothing");
     const int W = FIXED ? TW : P.img_w, H = FIXED ? TH : P.img_h;
     const int NT = (W + 15) >> 4;   // 16-pixel tile columns, the last one partial when W % 16 != 0 (<= 32: one mask word)
     const int VB = 3 * W / 4;       // 16-B vectors of a band
@@ -326,7 +346,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     static_assert(NPRIM <= 16, "one primitive per lane of a DPP row");
     __shared__ Scene S_[EPW];
     __shared__ __attribute__((aligned(16))) unsigned char stage_fixed[FIXED ? 4 * 12 * TW : 16];
-    extern __shared__ __attribute__((aligned(16))) unsigned char stage_dyn[];   // [4][12 W] when the size is a run-time value
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage_dyn[];   // [4][12 W] when the size is a run-time value (PLANES: [4][12 W + 4 W], colours then segmentation)
     constexpr int WPE = 4 / EPW;   // waves per env
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int e = wave / WPE, wsub = wave % WPE;
@@ -343,7 +363,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     __syncthreads();
     if (!live) return;
     const size_t img_bytes = (size_t)H * W * 3;
-    unsigned char *st = FIXED ? stage_fixed + wave * (12 * TW) : stage_dyn + wave * (4 * RB);
+    unsigned char *st = FIXED ? stage_fixed + wave * (12 * TW) : stage_dyn + wave * (PLANES ? 16 * W : 4 * RB);
+    unsigned char *sgst = st + 4 * RB;   // PLANES: the staged segmentation band
+    const int VS = W >> 2;               // PLANES: 16-B vectors of a segmentation band = of one row of a depth band (W of them)
     const int marker = __builtin_amdgcn_readfirstlane(S.marker);
     // co-resident workgroups start at different bands (hashed phase) so that their ray-cast (VALU-bound) and copy
     // (memory-bound) stretches overlap instead of all waves of a SIMD hitting the arm's rows together
@@ -362,6 +384,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     const float *cull = S.cull[cam][lane < NPRIM ? lane : 0];
     const u32x4 *bg = reinterpret_cast<const u32x4 *>(P.img_bg) + (size_t)cam * NB * VB;
     u32x4 *out = reinterpret_cast<u32x4 *>((cam ? P.img_top : P.img_front) + (size_t)env * img_bytes);
+    // PLANES: this camera's planes of this env, and their background (null pointer: plane not enabled -- wave-uniform)
+    const size_t plane_px = (size_t)H * W;
+    f32x4 *dplane = nullptr;
+    u32x4 *splane = nullptr;
+    const f32x4 *dbg = nullptr;
+    const u32x4 *sbg = nullptr;
+    if (PLANES) {
+        float *dp = cam ? PL.depth_top : PL.depth_front;
+        unsigned char *sp = cam ? PL.seg_top : PL.seg_front;
+        if (dp) { dplane = reinterpret_cast<f32x4 *>(dp + (size_t)env * plane_px); dbg = reinterpret_cast<const f32x4 *>(PL.bg_depth + (size_t)cam * plane_px); }
+        if (sp) { splane = reinterpret_cast<u32x4 *>(sp + (size_t)env * plane_px); sbg = reinterpret_cast<const u32x4 *>(PL.bg_seg + (size_t)cam * plane_px); }
+    }
+    // the depth band b (W vectors: 4 rows of W / 4) without the vectors of the tile columns in `skip` (a tile column = 4 vectors of each row)
+    auto copy_depth_band = [&](int b, unsigned skip) {
+        const f32x4 *s4 = dbg + (size_t)b * W;
+        f32x4 *d4 = dplane + (size_t)b * W;
+        for (int i = lane; i < W; i += 64) {
+            const int r = (i >= VS) + (i >= 2 * VS) + (i >= 3 * VS);
+            if (!((skip >> ((i - r * VS) >> 2)) & 1u)) __builtin_nontemporal_store(s4[i], d4 + i);
+        }
+    };
     for (int it = WPE == 4 ? wsub & 1 : 0; it < NB; it += BAND_STEP) {
         const int b = it + rot >= NB ? it + rot - NB : it + rot;
         u32x4 *dst = out + b * VB;
@@ -400,7 +443,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
 #pragma unroll
             for (int j = 0; j < NV; j++)
                 if (64 * j + lane < VB) __builtin_nontemporal_store(v[j], dst + 64 * j + lane);
+            if (PLANES) {
+                if (dplane) copy_depth_band(b, 0u);
+                if (splane)
+                    for (int i = lane; i < VS; i += 64) __builtin_nontemporal_store(sbg[(size_t)b * VS + i], splane + (size_t)b * VS + i);
+            }
             continue;
+        }
+        const unsigned U0 = U;
+        if (PLANES && splane) {
+            u32x4 *sgv = reinterpret_cast<u32x4 *>(sgst);
+            for (int i = lane; i < VS; i += 64) sgv[i] = sbg[(size_t)b * VS + i];
         }
         u32x4 *sv = reinterpret_cast<u32x4 *>(st);
 #pragma unroll
@@ -418,7 +471,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
             const f3 rdu = axpy(sx, CX, rbase);
             unsigned char *stpx = st + ty * RB + 3 * px;
             unsigned rgb = 0u;
-            const bool wrote = shade_span(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb) && (FIXED || pxt < W);
+            float tnear = 0.f;
+            int knear = -1;
+            bool mhit = false;
+            const bool wrote = shade_span<PLANES>(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb, tnear, knear, mhit) && (FIXED || pxt < W);
+            if (PLANES && pxt < W) {   // every pixel of a ray-cast tile: `m` holds all that can be seen in it, the base included
+                if (dplane) __builtin_nontemporal_store(fminf(tnear, PL.far), reinterpret_cast<float *>(dplane) + (size_t)(row0 + ty) * W + px);
+                if (splane) {
+                    const unsigned id = knear >= 0 ? (unsigned)knear + 2u : (rdu.z * rsq(dot(rdu, rdu)) < -1e-6f ? 1u : 0u);   // (the horizon rule of the background colours)
+                    sgst[ty * W + px] = (unsigned char)(id | (mhit ? 0x80u : 0u));
+                }
+            }
             if (wrote) {
                 stpx[0] = (unsigned char)rgb;
                 stpx[1] = (unsigned char)(rgb >> 8);
@@ -432,11 +495,79 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
 #pragma unroll
         for (int j = 0; j < NV; j++)
             if (64 * j + lane < VB) __builtin_nontemporal_store(sv[64 * j + lane], dst + 64 * j + lane);
+        if (PLANES) {
+            if (dplane) copy_depth_band(b, U0);
+            if (splane) {
+                const u32x4 *sgv = reinterpret_cast<const u32x4 *>(sgst);
+                for (int i = lane; i < VS; i += 64) __builtin_nontemporal_store(sgv[i], splane + (size_t)b * VS + i);
+            }
+        }
     }
     } while ((cam += CAM_STEP) < 2);
 }
 
-#if LCR_RENDER_PART != 1
+#if LCR_RENDER_PLANES
+// one pixel, every primitive of the scene: the nearest opaque surface -- t along the un-normalised ray, which is metres along the optical axis (1e30: sky) -- and the
+// segmentation byte of include/lcr.h
+DEV void trace_pixel(const LcrCam &C, const float (*boxc)[16], int nbox, int marker, float sx, float sy, float &t, unsigned &seg) {
+    const f3 ro = mk(C.px, C.py, C.pz);
+    const f3 d = mk(C.xx * sx + C.yx * sy - C.zx, C.xy * sx + C.yy * sy - C.zy, C.xz * sx + C.yz * sy - C.zz);
+    const bool down = d.z * rsq(dot(d, d)) < -1e-6f;   // the horizon rule of floor_or_sky
+    float tbest = down ? -ro.z * rcp(d.z) : 1e30f;
+    int kbest = -1;
+    bool mhit = false;
+    for (int k = 0; k < nbox; k++) {
+        float tmin, ld;
+        if (!box_hit(boxc[k], sx, sy, tbest, tmin, ld)) continue;
+        if (k == marker) mhit = true;   // (the marker is the last box: every opaque primitive has been seen)
+        else { tbest = tmin; kbest = k; }
+    }
+    t = tbest;
+    seg = (kbest >= 0 ? (unsigned)kbest + 2u : (down ? 1u : 0u)) | (mhit ? 0x80u : 0u);
+}
+
+// the background planes of the two observation cameras (floor, sky, the arm's base), rendered once at lcr_enable_image_planes into PL.bg_depth / PL.bg_seg ([2][H][W])
+__global__ __launch_bounds__(256) void lcr_render_bg_planes_kernel(LcrDev P, LcrCam front, LcrCam top, LcrPlanes PL) {
+    const int W = P.img_w, H = P.img_h;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= 2 * W * H) return;
+    const bool is_top = pix >= W * H;
+    const int p = is_top ? pix - W * H : pix;
+    const int row = p / W, px = p - row * W;
+    const LcrCam &C = is_top ? top : front;
+    const float sy = -(row + 0.5f - 0.5f * H) * C.s, sx = (px + 0.5f - 0.5f * W) * C.s;
+    f3 bc, bX, bY, bZ, bh;
+    base_box(bc, bX, bY, bZ, bh);
+    float boxc[1][16];
+    box_consts(C, bc, bX, bY, bZ, bh, 1.f, boxc[0]);
+    float t;
+    unsigned seg;
+    trace_pixel(C, boxc, 1, -1, sx, sy, t, seg);
+    PL.bg_depth[pix] = fminf(t, PL.far);
+    PL.bg_seg[pix] = (unsigned char)seg;
+}
+
+// one env, arbitrary camera / resolution, one thread per pixel, no culling, no cached background: the sibling of lcr_render_single_kernel.  Either output may be null
+__global__ __launch_bounds__(256) void lcr_render_single_planes_kernel(LcrDev P, LcrCam cam, int env, int W, int H, float far, float *depth, unsigned char *seg_out) {
+    __shared__ Scene S;
+    if (threadIdx.x == 0) build_scene(P, env, S);
+    __syncthreads();
+    if (threadIdx.x < NBOX && (int)threadIdx.x < S.nbox)
+        box_consts(cam, S.bc[threadIdx.x], S.bX[threadIdx.x], S.bY[threadIdx.x], S.bZ[threadIdx.x], S.bh[threadIdx.x], S.balpha[threadIdx.x], S.boxc[0][threadIdx.x]);
+    __syncthreads();
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= W * H) return;
+    const int v = pix / W, u = pix - v * W;
+    const float sx = (u + 0.5f - 0.5f * W) * cam.s, sy = -(v + 0.5f - 0.5f * H) * cam.s;
+    float t;
+    unsigned seg;
+    trace_pixel(cam, S.boxc[0], S.nbox, S.marker, sx, sy, t, seg);
+    if (depth) depth[pix] = fminf(t, far);
+    if (seg_out) seg_out[pix] = (unsigned char)seg;
+}
+#endif
+
+#if LCR_RENDER_SMALL
 // one env, arbitrary camera / resolution (render(), 640x640 camera_vizu): one thread per pixel, no culling, no cached background
 __global__ __launch_bounds__(256) void lcr_render_single_kernel(LcrDev P, LcrCam cam, int env, int W, int H, unsigned char *out) {
     __shared__ Scene S;
@@ -486,7 +617,7 @@ void launch_obs(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *s
     const size_t lds = TW ? 0 : (size_t)4 * 12 * P.img_w;
     hipLaunchKernelGGL((lcr_render_obs_kernel<COUNT, NV, EPW, TW, TH>), dim3((P.n + EPW - 1) / EPW), dim3(256), lds, (hipStream_t)stream, P, front, top);
 }
-#if LCR_RENDER_PART != 0
+#if LCR_RENDER_SIZED
 template <bool COUNT>
 void launch_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, void *stream) {
     const int W = P.img_w, epw = P.img_epw;
@@ -505,14 +636,55 @@ void launch_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, v
 #endif
 }  // namespace
 
-#if LCR_RENDER_PART != 0
+#if LCR_RENDER_SIZED
 void lcr_launch_render_obs_sized(const LcrDev &P, const LcrCam &front, const LcrCam &top, bool count, void *stream) {
     if (count) launch_obs_sized<true>(P, front, top, stream);
     else launch_obs_sized<false>(P, front, top, stream);
 }
 #endif
 
-#if LCR_RENDER_PART != 1
+#if LCR_RENDER_PLANES
+namespace {
+template <int NV, int EPW>
+void launch_obs_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream) {
+    const size_t lds = (size_t)4 * 16 * P.img_w;   // per wave: 12 W B of colours + 4 W B of segmentation
+    hipLaunchKernelGGL((lcr_render_obs_kernel<false, NV, EPW, 0, 0, LcrPlanes>), dim3((P.n + EPW - 1) / EPW), dim3(256), lds, (hipStream_t)stream, P, front, top, PL);
+}
+}  // namespace
+
+// colour frames + the enabled planes in one launch: the run-time-size builds at every size (320 x 240 included), same mappings as launch_obs_sized
+int lcr_launch_render_obs_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream) {
+    if (!P.img_front || !P.img_top || !PL.bg_depth || !PL.bg_seg) return (int)hipErrorInvalidValue;
+    const int nv = (3 * P.img_w / 4 + 63) / 64, epw = P.img_epw;
+    if (nv > 4) launch_obs_planes<6, 1>(P, front, top, PL, stream);
+    else if (nv > 2) launch_obs_planes<4, 1>(P, front, top, PL, stream);
+    else if (nv > 1) {
+        if (epw == 4) launch_obs_planes<2, 4>(P, front, top, PL, stream);
+        else if (epw == 2) launch_obs_planes<2, 2>(P, front, top, PL, stream);
+        else launch_obs_planes<2, 1>(P, front, top, PL, stream);
+    } else {
+        if (epw == 4) launch_obs_planes<1, 4>(P, front, top, PL, stream);
+        else if (epw == 2) launch_obs_planes<1, 2>(P, front, top, PL, stream);
+        else launch_obs_planes<1, 1>(P, front, top, PL, stream);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_bg_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream) {
+    hipLaunchKernelGGL(lcr_render_bg_planes_kernel, dim3((2 * P.img_w * P.img_h + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, front, top, PL);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_single_planes(const LcrDev &P, const LcrCam &cam, int env, int W, int H, float far, float *depth_dev, unsigned char *seg_dev, void *stream) {
+    hipLaunchKernelGGL(lcr_render_single_planes_kernel, dim3((W * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, cam, env, W, H, far, depth_dev, seg_dev);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+#endif
+
+#if LCR_RENDER_SMALL
 int lcr_launch_gather_terminal(const LcrDev &P, const int *ids_dev, int count, float *qpos_out, float *target_out, void *stream) {
     hipLaunchKernelGGL(lcr_gather_terminal_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, ids_dev, count, qpos_out, target_out);
     hipError_t e = hipGetLastError();

@@ -53,6 +53,8 @@ def _obs_spaces(sim, observation_mode):
     if observation_mode in ("image", "both"):
         subs["image_front"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)   # (240, 320, 3) unless VecSim was given an image_size
         subs["image_top"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)
+        for k in sim.plane_arrays():   # VecSim(image_planes=...): depth_front / depth_top in metres up to depth_far, segmentation_front / segmentation_top ids (include/lcr.h)
+            subs[k] = sp.Box(0.0, sim.depth_far, shape=sim.image_size, dtype=np.float32) if k.startswith("depth_") else sp.Box(0, 255, shape=sim.image_size, dtype=np.uint8)
     if observation_mode in ("state", "both"):
         subs[sim.cube_name] = sp.Box(-10.0, 10.0, shape=(3,), dtype=np.float32)
         if sim.task_name == "stack":
@@ -89,10 +91,12 @@ class LowCostRobotVecEnv(_SB3VecEnv):
         if self.observation_mode in ("image", "both"):
             o["image_front"] = sim.image_front.numpy()
             o["image_top"] = sim.image_top.numpy()
+            for k, a in sim.plane_arrays().items():
+                o[k] = a.numpy()
         # forced copies: the pinned mirror is overwritten by the next fetch and freed by close(), and SB3 keeps the returned arrays
         # in its rollout buffer (np.ascontiguousarray would hand out a VIEW of the mirror when num_envs == 1, where the transposed
         # (6, 1) view already counts as contiguous); the frames come from a device-to-host copy of their own
-        return {k: (o[k] if k.startswith("image_") else np.array(o[k], copy=True, order="C")) for k in self._keys}
+        return {k: (o[k] if k.startswith(("image_", "depth_", "segmentation_")) else np.array(o[k], copy=True, order="C")) for k in self._keys}
 
     def _obs(self):
         return self._obs_from(self.sim.fetch_host())
@@ -106,8 +110,11 @@ class LowCostRobotVecEnv(_SB3VecEnv):
         sim = self.sim
         img = self.observation_mode in ("image", "both")
         fr = tp = None
+        planes = {}
         if img and len(env_ids):
             fr, tp = sim.render_terminal(env_ids)
+            if sim.image_planes:
+                planes = sim.render_terminal_planes(env_ids)
         out = []
         for j, t in enumerate(tobs_rows):
             d = {"arm_qpos": t[0:6].copy(), "arm_qvel": t[6:12].copy()}
@@ -119,6 +126,8 @@ class LowCostRobotVecEnv(_SB3VecEnv):
                     d["cube_blue_pos"] = t[15:18].copy()
             if img:
                 d["image_front"], d["image_top"] = fr[j], tp[j]
+                for k, a in planes.items():
+                    d[k] = a[j]
             out.append({k: d[k] for k in self._keys})
         return out
 
@@ -267,8 +276,13 @@ class LowCostRobotVectorEnv:
                 ridx = np.nonzero(h["did_reset"])[0]
                 fin["image_front"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)   # (calloc'ed: pages of envs that were not reset are never touched)
                 fin["image_top"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)
+                for k, a in sim.plane_arrays().items():
+                    fin[k] = np.zeros((self.num_envs,) + sim.image_size, a.dtype)
                 if ridx.size:
                     fin["image_front"][ridx], fin["image_top"][ridx] = sim.render_terminal(ridx)
+                    if sim.image_planes:
+                        for k, a in sim.render_terminal_planes(ridx).items():
+                            fin[k][ridx] = a
             fin = {k: fin[k] for k in v._keys}
             infos["final_obs"] = fin
             infos["_final_obs"] = h["did_reset"].copy()

@@ -10,7 +10,9 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import ACTION_MODES, OBS_MODES, REWARD_TYPES, TASKS, LcrConfig, LcrHostView, LcrObsView, LcrOutView, check
+from ._capi import ACTION_MODES, OBS_MODES, REWARD_TYPES, TASKS, LcrConfig, LcrHostView, LcrObsView, LcrOutView, LcrPlanesView, check
+
+CAMERAS = {"camera_front": 0, "camera_top": 1, "camera_vizu": 2}
 
 
 def _vp(a):
@@ -86,6 +88,8 @@ class VecSim:
         finger_floor_condim=None,
         coop_share=None,
         image_size=None,
+        image_planes=(),
+        depth_far=10.0,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -94,6 +98,18 @@ class VecSim:
             raise ValueError(f"invalid observation_mode {observation_mode!r}")
         if reward_type not in REWARD_TYPES:
             raise ValueError(f"invalid reward_type {reward_type!r}")
+        # depth / segmentation planes beside the colour frames (lcr_enable_image_planes): checked here, before the library is asked for a device
+        if isinstance(image_planes, str) or any(p not in _capi.IMAGE_PLANES for p in image_planes):
+            raise ValueError(f"image_planes must be a tuple drawn from 'depth' and 'segmentation', got {image_planes!r}")
+        image_planes = tuple(p for p in _capi.IMAGE_PLANES if p in image_planes)   # (canonical order, no repeats)
+        if image_planes and observation_mode == "state":
+            raise ValueError("image_planes need image observations: observation_mode 'image' or 'both'")
+        try:
+            depth_far = float(depth_far)
+        except (TypeError, ValueError):
+            raise ValueError(f"depth_far must be a number of metres in (0, 1000], got {depth_far!r}") from None
+        if not (np.isfinite(depth_far) and 0.0 < depth_far <= 1000.0):
+            raise ValueError(f"depth_far must be finite and in (0, 1000] metres, got {depth_far!r}")
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -190,6 +206,22 @@ class VecSim:
         img = (N,) + self.image_size + (3,)
         self.image_front = DeviceArray(self, ov.image_front, img, np.uint8) if ov.image_front else None
         self.image_top = DeviceArray(self, ov.image_top, img, np.uint8) if ov.image_top else None
+        self.image_planes, self.depth_far = image_planes, depth_far
+        self.depth_front = self.depth_top = self.seg_front = self.seg_top = None
+        if image_planes:
+            try:
+                check(self.L.lcr_enable_image_planes(self.handle, sum(_capi.IMAGE_PLANES[p] for p in image_planes), depth_far))
+                pv = LcrPlanesView()
+                check(self.L.lcr_get_image_planes(self.handle, ctypes.byref(pv)))
+            except Exception:
+                self.close()
+                raise
+            self.depth_far = float(pv.depth_far)   # (as the library holds it: float32)
+            pl = (N,) + self.image_size
+            self.depth_front = DeviceArray(self, pv.depth_front, pl, np.float32) if pv.depth_front else None
+            self.depth_top = DeviceArray(self, pv.depth_top, pl, np.float32) if pv.depth_top else None
+            self.seg_front = DeviceArray(self, pv.seg_front, pl, np.uint8) if pv.seg_front else None
+            self.seg_top = DeviceArray(self, pv.seg_top, pl, np.uint8) if pv.seg_top else None
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -289,6 +321,53 @@ class VecSim:
         check(self.L.lcr_render_terminal(self.handle, _vp(ids), int(ids.size), _vp(front), _vp(top)))
         return front, top
 
+    def render_planes(self, env=0, camera="camera_front", width=320, height=240):
+        """depth and segmentation of one env, one ray per pixel (the sibling of render()): ((height, width) float32 metres along the optical axis, clipped at
+        depth_far; (height, width) uint8 ids, see include/lcr.h).  Works with or without image_planes."""
+        depth, seg = np.empty((height, width), np.float32), np.empty((height, width), np.uint8)
+        check(self.L.lcr_render_planes(self.handle, int(env), CAMERAS[camera], int(width), int(height), _vp(depth), _vp(seg)))
+        return depth, seg
+
+    def render_state_planes(self, qpos, target=None, camera="camera_front", width=320, height=240):
+        """depth and segmentation of an arbitrary pose (the sibling of render_state()); the far clip is depth_far when image_planes are enabled, else 10 m"""
+        q = np.ascontiguousarray(qpos, np.float64)
+        if q.shape != (self.nq,):
+            raise ValueError(f"qpos must have shape ({self.nq},)")
+        t = None if target is None else np.ascontiguousarray(target, np.float32)
+        depth, seg = np.empty((height, width), np.float32), np.empty((height, width), np.uint8)
+        check(self.L.lcr_render_state_planes(self.handle, CAMERAS[camera], int(width), int(height), _vp(q), _vp(t), _vp(depth), _vp(seg)))
+        return depth, seg
+
+    def render_terminal_planes(self, env_ids):
+        """the enabled planes of the last frames of the episodes the last step ended in the listed envs, one batch (the sibling of render_terminal(), same precondition):
+        a dict with the keys of observations() -- depth_front, depth_top (len(env_ids), H, W) float32 / segmentation_front, segmentation_top uint8"""
+        if not self.image_planes:
+            raise ValueError("render_terminal_planes: no image_planes are enabled")
+        ids = np.ascontiguousarray(env_ids, np.int32)
+        if ids.size and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():
+            raise ValueError("render_terminal_planes: every listed env must have finished an episode in the last step (did_reset)")
+        shape = (ids.size,) + self.image_size
+        d = "depth" in self.image_planes
+        s = "segmentation" in self.image_planes
+        df, dtp = (np.empty(shape, np.float32), np.empty(shape, np.float32)) if d else (None, None)
+        sf, stp = (np.empty(shape, np.uint8), np.empty(shape, np.uint8)) if s else (None, None)
+        check(self.L.lcr_render_terminal_planes(self.handle, _vp(ids), int(ids.size), _vp(df), _vp(dtp), _vp(sf), _vp(stp)))
+        out = {}
+        if d:
+            out["depth_front"], out["depth_top"] = df, dtp
+        if s:
+            out["segmentation_front"], out["segmentation_top"] = sf, stp
+        return out
+
+    def plane_arrays(self):
+        """the enabled planes as {observation key: DeviceArray}, in the key order of observations()"""
+        out = {}
+        if self.depth_front is not None:
+            out["depth_front"], out["depth_top"] = self.depth_front, self.depth_top
+        if self.seg_front is not None:
+            out["segmentation_front"], out["segmentation_top"] = self.seg_front, self.seg_top
+        return out
+
     def read_rows(self, arr, rows):
         """host copies of selected leading-axis rows of a device array (e.g. the frames of a few recorded envs): one small
         device-to-host copy per row instead of the whole array"""
@@ -330,6 +409,8 @@ class VecSim:
         if self.image_front is not None:
             obs["image_front"] = self.image_front.numpy()
             obs["image_top"] = self.image_top.numpy()
+            for k, a in self.plane_arrays().items():
+                obs[k] = a.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

@@ -328,6 +328,43 @@ int lcr_render_state(lcr_sim *sim, int camera, int width, int height, const doub
  * binding (VecSim.render_terminal) checks it and raises ValueError. */
 int lcr_render_terminal(lcr_sim *sim, const int32_t *env_ids_host, int count, uint8_t *front_host, uint8_t *top_host);
 
+/* == Depth and segmentation planes of the image observations (MuJoCo's Renderer.enable_depth_rendering / enable_segmentation_rendering, the renderer of
+ * reach_cube_env.py:112; the reference's envs never switch them on).  The frame kernel knows the nearest surface of every pixel it draws and the distance to it;
+ * with planes enabled it writes them beside the colours, in the same launch, at the configured frame size.
+ *   ray    of pixel (row, px): d = sx X + sy Y - Z for the camera axes X, Y, Z (un-normalised; sx, sy as the colours have them).  d . (-Z) = 1, so the ray parameter t
+ *          IS the distance along the optical axis in metres -- the z-depth a depth camera reports, not the radial distance.
+ *   depth  float32 metres: min(t of the nearest opaque surface, depth_far).  Floor: t = -ro.z / d.z where the normalised d.z < -1e-6 (the horizon rule of the
+ *          colours); sky: depth_far.  No near plane beyond t > 0.  depth_far is the caller's: finite, in (0, 1000] m.
+ *   seg    uint8: the low 7 bits are the id of the nearest opaque surface -- 0 sky, 1 floor, 2 .. 8 base_link, link_1 .. link_6 (the seven arm boxes), 9 the cube
+ *          (StackTwoCubes: the red one), 10 the second cube (StackTwoCubes only).  Bit 7 (0x80) is set where the translucent target marker (PushCube / PickPlaceCube)
+ *          covers the pixel in front of that surface; the marker never writes depth and never becomes the id, as it only blends into the colours.
+ *   layout [N][H][W] per camera, (H, W) = the size of the colour frames.  Memory: 2 x 4 B (depth) + 2 x 1 B (segmentation) per pixel and env beside 2 x 3 B of
+ *          colour -- 768 000 B per env at 320 x 240 beside 460 800 B. */
+enum { LCR_PLANE_DEPTH = 1, LCR_PLANE_SEGMENTATION = 2 };
+typedef struct lcr_planes_view {
+    uint32_t planes;                           /* LCR_PLANE_* bits in use; 0: no planes, everything below is 0 / NULL */
+    int32_t image_width, image_height;
+    float depth_far;
+    const float *depth_front, *depth_top;      /* device, [N][H][W], or NULL */
+    const uint8_t *seg_front, *seg_top;        /* device, [N][H][W], or NULL */
+} lcr_planes_view;
+
+/* Switch the planes on (`planes`: LCR_PLANE_* bits, at least one; depth_far in metres).  `planes` and `depth_far` are checked before the handle is looked at; then a NULL
+ * handle and a handle without image observations are refused -- all with LCR_ERR_INVALID and the argument's name in the message.  Allocates the plane buffers and the
+ * cached background planes (floor, sky, the arm's base) and ray-casts them from the current state.  From then on whatever draws the colour frames -- the step, reset and
+ * its masked no-op form -- draws the planes in the same launch, so they share the frames' stream ordering.  A second call with the same arguments does nothing, one
+ * with other arguments is refused: the planes are fixed for the life of the handle. */
+int lcr_enable_image_planes(lcr_sim *sim, uint32_t planes, float depth_far);
+/* The plane buffers; waits (on the handle's stream) for frames still being ray-cast on the second stream, as every entry point but the step does. */
+int lcr_get_image_planes(lcr_sim *sim, lcr_planes_view *out);
+/* One env / an arbitrary pose, any camera (0 front, 1 top, 2 vizu), any size, one ray per pixel: the siblings of the two single-frame calls above.  Either of
+ * depth_host[height][width] / seg_host[height][width] may be NULL.  They work without planes enabled; the far clip is the handle's depth_far when they are, else 10. */
+int lcr_render_planes(lcr_sim *sim, int env, int camera, int width, int height, float *depth_host, uint8_t *seg_host);
+int lcr_render_state_planes(lcr_sim *sim, int camera, int width, int height, const double *qpos_host, const float *target_host, float *depth_host, uint8_t *seg_host);
+/* The batched sibling of the terminal-frames call above (same precondition): the enabled planes of the TERMINAL poses of the listed envs, [count][H][W] each.  Needs planes
+ * enabled; a pointer of a plane that is not enabled may be NULL (and is not written). */
+int lcr_render_terminal_planes(lcr_sim *sim, const int32_t *env_ids_host, int count, float *depth_front, float *depth_top, uint8_t *seg_front, uint8_t *seg_top);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */

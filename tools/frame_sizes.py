@@ -1,9 +1,11 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task]
+    python tools/frame_sizes.py [n_envs] [task] [--planes]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
   (ii) step + frames, closed loop (a sync after every step, what a policy that reads the frames sees) and open loop (steps enqueued back to back): env-steps/s.
+--planes: (i) once more with the depth plane, the segmentation plane and both switched on (VecSim(image_planes=...)): the frame kernel then writes 3 + 4 / 3 + 1 / 3 + 4 + 1 bytes
+per pixel, so a store-bound kernel would take 7/3, 4/3 and 8/3 of the plain time; the measured ratio is printed beside that.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -14,23 +16,20 @@ import numpy as np  # noqa: E402
 
 from gym_lowcostrobot_amd import VecSim  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
-task = sys.argv[2] if len(sys.argv) > 2 else "stack"
+PLANES = "--planes" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--planes"]
+n = int(args[0]) if len(args) > 0 else 32768
+task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
 SOAK_S, WINDOWS, STEPS = 2.0, 7, 60
 print(f"frame sizes: {task}, {n} envs, default preset, LCR_RENDER_EPW={os.environ.get('LCR_RENDER_EPW', '(by frame size)')}")
 print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
 rows = []
-for H, W in SIZES:
-    sim = VecSim(task, n, observation_mode="both", image_size=(H, W))
-    assert sim.image_size == (H, W)
-    act = [sim.alloc_actions() for _ in range(8)]
-    for t, a in enumerate(act):
-        sim.fill_random_actions(a, 1, t)
-    for t in range(12):
-        sim.step_device(act[t % 8].ptr)
+
+
+def frame_kernel_ms(sim):
+    """the frame kernel alone: windows of ten masked no-op resets after a soak -> (median, min, max) ms per launch"""
     mask = np.zeros(n, np.uint8)
-    nbytes = 2 * H * W * 3 * n
     sim.reset(mask=mask); sim.sync()
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < SOAK_S:
@@ -43,7 +42,21 @@ for H, W in SIZES:
         for _ in range(10):
             sim.reset(mask=mask)
         w.append(sim.timer_end() / 10)
-    ms = float(np.median(w))
+    return float(np.median(w)), min(w), max(w)
+
+
+plane_rows = []
+for H, W in SIZES:
+    sim = VecSim(task, n, observation_mode="both", image_size=(H, W))
+    assert sim.image_size == (H, W)
+    act = [sim.alloc_actions() for _ in range(8)]
+    for t, a in enumerate(act):
+        sim.fill_random_actions(a, 1, t)
+    for t in range(12):
+        sim.step_device(act[t % 8].ptr)
+    nbytes = 2 * H * W * 3 * n
+    ms, wmin, wmax = frame_kernel_ms(sim)
+    w = [wmin, wmax]
     sim.sync()
     t0 = time.perf_counter()
     for t in range(STEPS):
@@ -60,6 +73,20 @@ for H, W in SIZES:
     for a in act:
         sim.free(a)
     sim.close()
+    for planes, bpp in ((("depth",), 7), (("segmentation",), 4), (("depth", "segmentation"), 8)) if PLANES else ():
+        sim = VecSim(task, n, observation_mode="both", image_size=(H, W), image_planes=planes)
+        act = sim.alloc_actions()
+        for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+            sim.fill_random_actions(act, 1, t % 8)
+            sim.step_device(act.ptr)
+        pms, pmin, pmax = frame_kernel_ms(sim)
+        plane_rows.append((H, W, "+".join(planes), pms, pmin, pmax, pms / ms, bpp / 3, 2 * H * W * bpp * n, 2 * H * W * (bpp - 3)))
+        sim.free(act)
+        sim.close()
 base = rows[0][2]
 for H, W, ms in rows[1:]:
     print(f"  {H}x{W}: {ms / base:.3f} of the 240x320 kernel's time for {H * W / (240 * 320):.3f} of its bytes" + ("" if ms < base else "   <-- NOT faster than 240x320"))
+if PLANES:
+    print(f"frame kernel with planes ({n} envs): ms per launch, ratio to the plain kernel of the same size beside the ratio of the bytes written, TB/s, plane bytes per env")
+    for H, W, name, pms, pmin, pmax, ratio, bytes_ratio, nb, per_env in plane_rows:
+        print(f"{H:4d}x{W:<4d} {name:>19s} {pms:8.3f} (min {pmin:.3f} max {pmax:.3f})  x{ratio:.2f} of plain (bytes x{bytes_ratio:.2f})  {nb / pms / 1e9:6.2f} TB/s  {per_env:8d} B/env of planes")
