@@ -29,6 +29,9 @@ IMG_H, IMG_W = 240, 320   # LCR_IMG_H / LCR_IMG_W: the default size of the image
 PLANE_DEPTH, PLANE_SEGMENTATION = 1, 2   # LCR_PLANE_*: bits of lcr_enable_image_planes
 IMAGE_PLANES = {"depth": PLANE_DEPTH, "segmentation": PLANE_SEGMENTATION}
 
+LOOK_MAX_VARIANTS = 64   # LCR_LOOK_MAX_VARIANTS
+LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
+
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 
 # every symbol include/lcr.h declares (tests check the .so exports exactly these)
@@ -39,6 +42,7 @@ SYMBOLS = [
     "lcr_memcpy_h2d", "lcr_memcpy_d2h", "lcr_timer_begin", "lcr_timer_end", "lcr_fill_random_actions",
     "lcr_calibrate_copy", "lcr_render", "lcr_render_state", "lcr_render_terminal", "lcr_step_kernel_family",
     "lcr_enable_image_planes", "lcr_get_image_planes", "lcr_render_planes", "lcr_render_state_planes", "lcr_render_terminal_planes",
+    "lcr_look_variant_default", "lcr_enable_look", "lcr_set_look", "lcr_get_look",
 ]
 
 
@@ -110,6 +114,77 @@ class LcrPlanesView(ctypes.Structure):
         ("seg_front", ctypes.c_void_p),    # [N][H][W] uint8 ids
         ("seg_top", ctypes.c_void_p),
     ]
+
+
+class LookVariant(ctypes.Structure):
+    """lcr_look_variant: everything the cached background of the frames depends on (include/lcr.h).  Index 0 = camera_front, 1 = camera_top."""
+    _fields_ = [
+        ("cam_dpos", (ctypes.c_float * 3) * 2),    # metres, world frame, added to the scene camera's position
+        ("cam_drot", (ctypes.c_float * 3) * 2),    # rotation vector, world frame
+        ("fovy_deg", ctypes.c_float * 2),
+        ("floor_rgb", (ctypes.c_float * 3) * 2),   # checker cells: odd, even
+        ("sky_rgb", ctypes.c_float * 3),
+        ("sky_slope", ctypes.c_float * 3),
+        ("ambient", ctypes.c_float),
+        ("diffuse", ctypes.c_float),
+        ("arm_rgb", ctypes.c_float * 3),
+        ("finger_rgb", ctypes.c_float * 3),
+    ]
+
+    def as_dict(self):
+        import numpy as np
+
+        return {name: (np.array(getattr(self, name), np.float32) if not isinstance(getattr(self, name), float) else float(getattr(self, name))) for name, _ in self._fields_}
+
+    @classmethod
+    def from_any(cls, v):
+        """a LookVariant, or a dict of some of its fields over the default variant"""
+        if isinstance(v, cls):
+            return v
+        import numpy as np
+
+        out = cls()
+        check(load().lcr_look_variant_default(ctypes.byref(out)))
+        shapes = {"cam_dpos": (2, 3), "cam_drot": (2, 3), "fovy_deg": (2,), "floor_rgb": (2, 3), "sky_rgb": (3,), "sky_slope": (3,), "arm_rgb": (3,), "finger_rgb": (3,)}
+        for name, val in dict(v).items():
+            if name in ("ambient", "diffuse"):
+                setattr(out, name, float(val))
+            elif name in shapes:
+                a = np.broadcast_to(np.asarray(val, np.float32), shapes[name])
+                fld = getattr(out, name)
+                for idx in np.ndindex(*shapes[name]):
+                    if len(idx) == 1:
+                        fld[idx[0]] = float(a[idx])
+                    else:
+                        fld[idx[0]][idx[1]] = float(a[idx])
+            else:
+                raise ValueError(f"unknown look variant field {name!r}")
+        return out
+
+
+class LookSampler(ctypes.Structure):
+    """lcr_look_sampler: per-channel uniform boxes of the per-env colours, redrawn at every reset of an env"""
+    _fields_ = [("seed", ctypes.c_uint64)] + [(f"{g}_{e}", ctypes.c_float * 3) for g in ("cube", "cube2", "marker") for e in ("lo", "hi")]
+
+    @classmethod
+    def from_any(cls, v):
+        """a LookSampler, or a dict: seed, and per group cube / cube2 / marker a (lo, hi) pair under its name or `<group>_lo` / `<group>_hi`; a group not named keeps its task colour"""
+        if isinstance(v, cls):
+            return v
+        import numpy as np
+
+        v = dict(v)
+        out = cls()
+        out.seed = int(v.pop("seed", 0))
+        for g, base in (("cube", LOOK_TASK_RGB[0:3]), ("cube2", LOOK_TASK_RGB[3:6]), ("marker", LOOK_TASK_RGB[6:9])):
+            lo, hi = v.pop(g, (base, base))
+            lo, hi = v.pop(g + "_lo", lo), v.pop(g + "_hi", hi)
+            for i in range(3):
+                getattr(out, g + "_lo")[i] = float(np.broadcast_to(np.asarray(lo, np.float32), (3,))[i])
+                getattr(out, g + "_hi")[i] = float(np.broadcast_to(np.asarray(hi, np.float32), (3,))[i])
+        if v:
+            raise ValueError(f"unknown look sampler fields {sorted(v)}")
+        return out
 
 
 class LcrOutView(ctypes.Structure):
@@ -224,6 +299,10 @@ def load():
     L.lcr_render_planes.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     L.lcr_render_state_planes.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     L.lcr_render_terminal_planes.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
+    L.lcr_look_variant_default.argtypes = [ctypes.POINTER(LookVariant)]
+    L.lcr_enable_look.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LookVariant), ctypes.POINTER(LookSampler)]
+    L.lcr_set_look.argtypes = [vp, vp, vp, vp]
+    L.lcr_get_look.argtypes = [vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

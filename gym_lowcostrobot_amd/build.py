@@ -37,6 +37,8 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          ("lcr_render.hip", "lcr_render.o", ["-DLCR_RENDER_PART=0"]), ("lcr_render.hip", "lcr_render_sizes.o", ["-DLCR_RENDER_PART=1"]),
          # the frame kernels that also draw the depth / segmentation planes (run-time sizes only), their background and single-frame kernels
          ("lcr_render.hip", "lcr_render_planes.o", ["-DLCR_RENDER_PART=3"]),
+         # the kernels that draw with a look (lcr_enable_look): frame kernels with and without planes, the backgrounds of the variants, the single-frame and redraw kernels
+         ("lcr_render.hip", "lcr_render_look.o", ["-DLCR_RENDER_PART=4"]),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),

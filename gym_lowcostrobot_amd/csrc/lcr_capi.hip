@@ -34,18 +34,43 @@ int fail(int code, const char *fmt, ...) {
 }  // namespace
 
 namespace {
-void cam_finish(LcrCam &c, const double p[3], double X[3], double Y[3], int height) {
+// `rot` (or null): a rotation vector, world frame, the finished axes are turned by (lcr_look_variant.cam_drot); `fovy_deg` 45: MuJoCo's default camera fovy
+void cam_finish(LcrCam &c, const double p[3], double X[3], double Y[3], int height, const double *rot = nullptr, double fovy_deg = 45.0) {
     auto nrm = [](double *v) { double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); v[0] /= n; v[1] /= n; v[2] /= n; };
     nrm(X);
     double d = X[0] * Y[0] + X[1] * Y[1] + X[2] * Y[2];
     for (int i = 0; i < 3; i++) Y[i] -= d * X[i];
     nrm(Y);
     double Z[3] = {X[1] * Y[2] - X[2] * Y[1], X[2] * Y[0] - X[0] * Y[2], X[0] * Y[1] - X[1] * Y[0]};
+    const double th = rot ? std::sqrt(rot[0] * rot[0] + rot[1] * rot[1] + rot[2] * rot[2]) : 0.0;
+    if (th > 0.0) {   // Rodrigues: v cos + (k x v) sin + k (k . v)(1 - cos); no rotation leaves the axes bit for bit
+        const double k[3] = {rot[0] / th, rot[1] / th, rot[2] / th}, cs = std::cos(th), sn = std::sin(th);
+        for (double *v : {X, Y, Z}) {
+            const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+            const double cr[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+            for (int i = 0; i < 3; i++) v[i] = v[i] * cs + cr[i] * sn + k[i] * kv * (1.0 - cs);
+        }
+    }
     c.px = (float)p[0]; c.py = (float)p[1]; c.pz = (float)p[2];
     c.xx = (float)X[0]; c.xy = (float)X[1]; c.xz = (float)X[2];
     c.yx = (float)Y[0]; c.yy = (float)Y[1]; c.yz = (float)Y[2];
     c.zx = (float)Z[0]; c.zy = (float)Z[1]; c.zz = (float)Z[2];
-    c.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);  // MuJoCo default camera fovy = 45 deg
+    // (45 degrees keeps its own expression: the scene cameras' `s` stays the constant it has always been, whatever the compiler makes of the general one)
+    if (fovy_deg == 45.0) c.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);  // MuJoCo default camera fovy = 45 deg
+    else c.s = (float)(2.0 * std::tan(0.5 * fovy_deg * M_PI / 180.0) / height);
+}
+// scene pose of observation camera `which` (0 camera_front, 1 camera_top; reach_cube.xml:29-30 and siblings)
+void scene_cam_pose(int which, double p[3], double X[3], double Y[3]) {
+    static const double P[2][3] = {{0.049, 0.5, 0.225}, {0, 0.1, 0.6}}, XX[2][3] = {{-0.998, 0.056, -0.000}, {1, 0, 0}}, YY[2][3] = {{-0.019, -0.335, 0.942}, {0, 1, 0}};
+    for (int i = 0; i < 3; i++) { p[i] = P[which][i]; X[i] = XX[which][i]; Y[i] = YY[which][i]; }
+}
+// observation camera `which` of a look variant for frames `height` rows high: the scene camera moved by cam_dpos, turned by cam_drot, with the variant's fovy
+void make_look_camera(const lcr_look_variant &v, int which, int height, LcrCam &out) {
+    double p[3], X[3], Y[3];
+    scene_cam_pose(which, p, X, Y);
+    double rot[3];
+    for (int i = 0; i < 3; i++) { p[i] += (double)v.cam_dpos[which][i]; rot[i] = (double)v.cam_drot[which][i]; }
+    cam_finish(out, p, X, Y, height, rot, (double)v.fovy_deg[which]);
 }
 // cameras of the scene files (reach_cube.xml:29-31 and siblings)
 void make_cameras(int task, int img_h, LcrCam &front, LcrCam &top, LcrCam &vizu) {
@@ -102,10 +127,27 @@ struct lcr_sim {
     uint32_t planes;             // LCR_PLANE_* bits in use, 0: none
     LcrPlanes pl;
     void *planes_mem;
+    // the look (lcr_enable_look): one allocation, fixed for the life of the handle.  A look is ten words per env, [10][N]: row 0 the variant, rows 1 .. 9 the colours
+    int look_K;                  // variants, 0: no look
+    void *look_mem;
+    LcrLook look;                // the arguments of the kernels that draw with the envs' current looks
+    int *look_cur, *look_term;   // current / terminal looks
+    unsigned *look_episode;      // [N]
+    int *snap_look[2];           // beside snap_qpos / snap_target
+    LcrLookSampler look_sm;
+    lcr_look_variant *look_variants;   // host copies of the arguments of lcr_enable_look
+    lcr_look_sampler look_sampler;
+    bool look_has_sampler;
 };
 
 // whatever draws the handle's colour frames draws its enabled planes in the same launch
-static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream) {
+// (`look`: the looks to draw P's envs with when they are not the current ones -- a snapshot)
+static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look = nullptr) {
+    if (s->look_K) {
+        LcrLook LK = s->look;
+        if (look) { LK.variant = look; LK.rgb = (const float *)(look + P.n); }
+        return lcr_launch_render_obs_look(P, LK, s->planes ? &s->pl : nullptr, stream);
+    }
     if (s->planes) return lcr_launch_render_obs_planes(P, s->cam_front, s->cam_top, s->pl, stream);
     return lcr_launch_render_obs(P, s->cam_front, s->cam_top, stream);
 }
@@ -523,6 +565,8 @@ void lcr_destroy(lcr_sim *s) {
     if (s->render_dev) (void)hipFree(s->render_dev);
     if (s->term_stage) (void)hipFree(s->term_stage);
     if (s->planes_mem) (void)hipFree(s->planes_mem);
+    if (s->look_mem) (void)hipFree(s->look_mem);
+    free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
     delete s;
@@ -560,6 +604,10 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
     if (seeds_host) HIPCHK(hipMemcpyAsync(s->seeds_dev, seeds_host, N * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
     int rc = lcr_launch_reset(s->dev, mask_host ? s->mask_dev : nullptr, seeds_host ? s->seeds_dev : nullptr, 0, 0, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "reset kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (s->look_K) {   // the reset envs count an episode and -- with a sampler -- draw its look
+        rc = lcr_launch_look_redraw(s->dev.n, s->dev.env_off, mask_host ? s->mask_dev : nullptr, 0, s->look_sm, s->look_cur, s->look_episode, nullptr, s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "look kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     if (s->has_images) {
         rc = launch_frames(s, s->dev, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -574,6 +622,10 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
     if (!action_dev) return fail(LCR_ERR_INVALID, "action is NULL");
     int rc = lcr_launch_step(s->dev, action_dev, s->ee_mode, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "step kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (s->look_K) {   // envs the step has auto-reset: their look becomes the terminal look, they count an episode and draw its look -- before the snapshot below
+        rc = lcr_launch_look_redraw(s->dev.n, s->dev.env_off, s->dev.did_reset, 0, s->look_sm, s->look_cur, s->look_episode, s->look_term, s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "look kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     if (s->has_images && s->rstream) {
         // the frame kernel reads qpos and target only: snapshot them (2.7 MB for 32 768 StackTwoCubes envs against 15 GB of frames), then ray-cast on the second stream while
         // this stream goes on with the next step.  Two snapshots in turn; the one about to be overwritten was read by the frames of two steps ago.
@@ -582,11 +634,13 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         if (s->snap_used[p]) HIPCHK(hipStreamWaitEvent(s->stream, s->ev_rdone[p], 0));
         HIPCHK(hipMemcpyAsync(s->snap_qpos[p], s->dev.qpos, sizeof(float) * (size_t)s->nq * N, hipMemcpyDeviceToDevice, s->stream));
         HIPCHK(hipMemcpyAsync(s->snap_target[p], s->dev.target, sizeof(float) * 3 * N, hipMemcpyDeviceToDevice, s->stream));
+        // (and the looks, 40 B per env: the redraw of the next step must not reach the frames of this one)
+        if (s->look_K) HIPCHK(hipMemcpyAsync(s->snap_look[p], s->look_cur, sizeof(int) * 10 * N, hipMemcpyDeviceToDevice, s->stream));
         HIPCHK(hipEventRecord(s->ev_snap[p], s->stream));
         HIPCHK(hipStreamWaitEvent(s->rstream, s->ev_snap[p], 0));
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
-        rc = launch_frames(s, R, s->rstream);
+        rc = launch_frames(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
@@ -779,6 +833,14 @@ int lcr_fill_random_actions(lcr_sim *s, float *action_dev, uint64_t seed, uint64
     return LCR_OK;
 }
 
+// the variant env `env` points at (a synchronous 4-byte read)
+static int look_variant_of(lcr_sim *s, int env, int *v) {
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(v, s->look_cur + env, sizeof(int), hipMemcpyDeviceToHost));
+    if (*v < 0 || *v >= s->look_K) return fail(LCR_ERR_HIP, "env %d points at variant %d of %d", env, *v, s->look_K);
+    return LCR_OK;
+}
+
 int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *rgb_host) {
     SIMCHK(s);
     if (!rgb_host) return fail(LCR_ERR_INVALID, "rgb_host is NULL");
@@ -795,7 +857,15 @@ int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *
         if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
         s->render_bytes = bytes;
     }
-    int rc = lcr_launch_render_single(s->dev, cam, env, width, height, s->render_dev, s->stream);
+    int rc;
+    if (s->look_K) {   // env's own look: cameras 0 and 1 are its variant's, camera_vizu stays where it is; the variant's colours and light, the env's colours
+        if (camera < 2) {
+            int v = 0;
+            if (int lr = look_variant_of(s, env, &v)) return lr;
+            make_look_camera(s->look_variants[v], camera, height, cam);
+        }
+        rc = lcr_launch_render_single_look(s->dev, cam, env, width, height, s->render_dev, s->look, env, s->dev.n, s->stream);
+    } else rc = lcr_launch_render_single(s->dev, cam, env, width, height, s->render_dev, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(rgb_host, s->render_dev, bytes, hipMemcpyDeviceToHost));
@@ -847,7 +917,7 @@ int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint
     if (cap == 0) return LCR_OK;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_ids = 0, o_q = al(sizeof(int) * cap), o_t = o_q + al(sizeof(float) * s->nq * cap), o_f = o_t + al(sizeof(float) * 3 * cap),
-                 o_tp = o_f + al(img * cap), need = o_tp + al(img * cap);
+                 o_tp = o_f + al(img * cap), o_lk = o_tp + al(img * cap), need = o_lk + (s->look_K ? al(sizeof(int) * 10 * cap) : 0);   // (o_lk: the terminal looks of the listed envs)
     if (need > s->term_stage_bytes) {
         if (s->term_stage) (void)hipFree(s->term_stage);
         s->term_stage = nullptr; s->term_stage_bytes = 0;
@@ -867,7 +937,13 @@ int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint
         P1.target = (float *)(base + o_t);
         P1.img_front = (unsigned char *)(base + o_f);
         P1.img_top = (unsigned char *)(base + o_tp);
-        rc = lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream);
+        if (s->look_K) {   // the episode that ended is drawn as it looked
+            rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
+            if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+            LcrLook LK = s->look;
+            LK.variant = (const int *)(base + o_lk); LK.rgb = (const float *)(base + o_lk) + c;
+            rc = lcr_launch_render_obs_look(P1, LK, nullptr, s->stream);
+        } else rc = lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         HIPCHK(hipMemcpyAsync(front_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipMemcpyAsync(top_host + (size_t)done * img, base + o_tp, img * c, hipMemcpyDeviceToHost, s->stream));
@@ -906,9 +982,10 @@ int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
     const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const bool dep = planes & LCR_PLANE_DEPTH, seg = planes & LCR_PLANE_SEGMENTATION;
+    const size_t nbg = s->look_K ? (size_t)s->look_K : 1;   // with a look: the background planes of every variant's cameras, [K][2][H][W]
     size_t off = 0;
-    const size_t o_bgd = off; off += al(2 * px * sizeof(float));
-    const size_t o_bgs = off; off += al(2 * px);
+    const size_t o_bgd = off; off += al(nbg * 2 * px * sizeof(float));
+    const size_t o_bgs = off; off += al(nbg * 2 * px);
     const size_t o_d0 = off; if (dep) off += al(N * px * sizeof(float));
     const size_t o_d1 = off; if (dep) off += al(N * px * sizeof(float));
     const size_t o_s0 = off; if (seg) off += al(N * px);
@@ -926,8 +1003,14 @@ int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
     PL.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
     PL.far = depth_far;
     // the background planes, then colours and planes of the current state
-    int rc = lcr_launch_render_bg_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
-    if (!rc) rc = lcr_launch_render_obs_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
+    int rc;
+    if (s->look_K) {
+        rc = lcr_launch_render_bg_planes_look(s->dev, s->look, s->look_K, PL, s->stream);
+        if (!rc) rc = lcr_launch_render_obs_look(s->dev, s->look, &PL, s->stream);
+    } else {
+        rc = lcr_launch_render_bg_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
+        if (!rc) rc = lcr_launch_render_obs_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
+    }
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
     if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "drawing the image planes failed: %s", hipGetErrorString((hipError_t)rc)); }
     s->pl = PL;
@@ -953,9 +1036,15 @@ int lcr_get_image_planes(lcr_sim *s, lcr_planes_view *out) {
 }
 
 // one frame's planes of the pose arrays of `P` (env `env`), drawn into the scratch frame and copied to the host
-static int render_planes_of(lcr_sim *s, const LcrDev &P, int env, int camera, int width, int height, size_t o_seg, float *depth_host, uint8_t *seg_host) {
+// (`look_env` >= 0: with that env's look, i.e. through its variant's camera when `camera` is an observation camera -- colours and light do not show in the planes)
+static int render_planes_of(lcr_sim *s, const LcrDev &P, int env, int camera, int width, int height, size_t o_seg, float *depth_host, uint8_t *seg_host, int look_env = -1) {
     LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
     cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
+    if (look_env >= 0 && s->look_K && camera < 2) {
+        int v = 0;
+        if (int lr = look_variant_of(s, look_env, &v)) return lr;
+        make_look_camera(s->look_variants[v], camera, height, cam);
+    }
     const size_t px = (size_t)width * height;
     const float far = s->planes ? s->pl.far : 10.f;
     int rc = lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_host ? (float *)s->render_dev : nullptr, seg_host ? s->render_dev + o_seg : nullptr, s->stream);
@@ -974,7 +1063,7 @@ int lcr_render_planes(lcr_sim *s, int env, int camera, int width, int height, fl
     if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
     const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255;
     if (int rc = ensure_render_scratch(s, o_seg + px)) return rc;
-    return render_planes_of(s, s->dev, env, camera, width, height, o_seg, depth_host, seg_host);
+    return render_planes_of(s, s->dev, env, camera, width, height, o_seg, depth_host, seg_host, env);
 }
 
 int lcr_render_state_planes(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, float *depth_host, uint8_t *seg_host) {
@@ -1022,6 +1111,7 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
     const size_t o_d1 = off; if (dep) off += al(px * sizeof(float) * cap);
     const size_t o_s0 = off; if (seg) off += al(px * cap);
     const size_t o_s1 = off; if (seg) off += al(px * cap);
+    const size_t o_lk = off; if (s->look_K) off += al(sizeof(int) * 10 * cap);   // the terminal looks of the listed envs
     if (off > s->term_stage_bytes) {
         if (s->term_stage) (void)hipFree(s->term_stage);
         s->term_stage = nullptr; s->term_stage_bytes = 0;
@@ -1046,7 +1136,13 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
         PL1.depth_top = dep ? (float *)(base + o_d1) : nullptr;
         PL1.seg_front = seg ? (unsigned char *)(base + o_s0) : nullptr;
         PL1.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
-        rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
+        if (s->look_K) {
+            rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
+            if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+            LcrLook LK = s->look;
+            LK.variant = (const int *)(base + o_lk); LK.rgb = (const float *)(base + o_lk) + c;
+            rc = lcr_launch_render_obs_look(P1, LK, &PL1, s->stream);
+        } else rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         if (dep) {
             HIPCHK(hipMemcpyAsync(depth_front + (size_t)done * px, base + o_d0, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
@@ -1058,6 +1154,192 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
         }
         HIPCHK(hipStreamSynchronize(s->stream));
     }
+    return LCR_OK;
+}
+
+// ---- the look of the image observations ----
+
+// (this file is compiled with -ffast-math: NaN and infinity are told by their exponent bits, read back through a volatile word so that the test is not folded away)
+static bool finite_f(float x) { uint32_t b; memcpy(&b, &x, sizeof b); volatile uint32_t vb = b; return (vb & 0x7f800000u) != 0x7f800000u; }
+static bool in_range(const float *v, int n, float lo, float hi) {
+    for (int i = 0; i < n; i++)
+        if (!finite_f(v[i]) || v[i] < lo || v[i] > hi) return false;
+    return true;
+}
+
+int lcr_look_variant_default(lcr_look_variant *v) {
+    if (!v) return fail(LCR_ERR_INVALID, "v is NULL");
+    memset(v, 0, sizeof *v);
+    v->fovy_deg[0] = v->fovy_deg[1] = 45.f;
+    const float odd[3] = {0.2f, 0.3f, 0.4f}, even[3] = {0.1f, 0.2f, 0.3f}, sky[3] = {0.15f, 0.25f, 0.35f};
+    for (int i = 0; i < 3; i++) {
+        v->floor_rgb[0][i] = odd[i]; v->floor_rgb[1][i] = even[i];
+        v->sky_rgb[i] = sky[i]; v->sky_slope[i] = sky[i];
+        v->arm_rgb[i] = 0.8f; v->finger_rgb[i] = 0.75f;
+    }
+    v->ambient = 0.3f; v->diffuse = 0.6f;
+    return LCR_OK;
+}
+
+// the task's colours (reach_cube.xml:26 / stack_two_cubes.xml:34 / push_cube.xml:35): cube, second cube, target marker
+static const float LOOK_TASK_RGB[9] = {0.5f, 0.f, 0.f, 0.f, 0.f, 0.5f, 0.f, 0.f, 1.f};
+
+int lcr_enable_look(lcr_sim *s, int n_variants, const lcr_look_variant *variants, const lcr_look_sampler *sampler) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (n_variants < 1 || n_variants > LCR_LOOK_MAX_VARIANTS) return fail(LCR_ERR_INVALID, "n_variants must lie in 1 .. %d, got %d", LCR_LOOK_MAX_VARIANTS, n_variants);
+    if (!variants) return fail(LCR_ERR_INVALID, "variants_host is NULL");
+    for (int k = 0; k < n_variants; k++) {
+        const lcr_look_variant &v = variants[k];
+        if (!in_range(&v.cam_dpos[0][0], 6, -0.2f, 0.2f)) return fail(LCR_ERR_INVALID, "variant %d: cam_dpos must be finite and within +-0.2 m per component", k);
+        for (int c = 0; c < 2; c++) {
+            const float *r = v.cam_drot[c];
+            if (!in_range(r, 3, -0.5f, 0.5f) || std::sqrt((double)r[0] * r[0] + (double)r[1] * r[1] + (double)r[2] * r[2]) > 0.5)
+                return fail(LCR_ERR_INVALID, "variant %d: cam_drot must be finite and at most 0.5 rad long", k);
+        }
+        if (!in_range(v.fovy_deg, 2, 20.f, 90.f)) return fail(LCR_ERR_INVALID, "variant %d: fovy_deg must be finite and in [20, 90]", k);
+        if (!in_range(&v.floor_rgb[0][0], 6, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "variant %d: floor_rgb must be finite and in [0, 1]", k);
+        if (!in_range(v.sky_rgb, 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "variant %d: sky_rgb must be finite and in [0, 1]", k);
+        if (!in_range(v.sky_slope, 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "variant %d: sky_slope must be finite and in [0, 1]", k);
+        if (!in_range(&v.ambient, 1, 0.f, 1.5f)) return fail(LCR_ERR_INVALID, "variant %d: ambient must be finite and in [0, 1.5]", k);
+        if (!in_range(&v.diffuse, 1, 0.f, 1.5f)) return fail(LCR_ERR_INVALID, "variant %d: diffuse must be finite and in [0, 1.5]", k);
+        if (!in_range(v.arm_rgb, 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "variant %d: arm_rgb must be finite and in [0, 1]", k);
+        if (!in_range(v.finger_rgb, 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "variant %d: finger_rgb must be finite and in [0, 1]", k);
+    }
+    if (sampler) {
+        const float *lo[3] = {sampler->cube_lo, sampler->cube2_lo, sampler->marker_lo}, *hi[3] = {sampler->cube_hi, sampler->cube2_hi, sampler->marker_hi};
+        const char *nm[3] = {"cube", "cube2", "marker"};
+        for (int g = 0; g < 3; g++) {
+            if (!in_range(lo[g], 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "sampler: %s_lo must be finite and in [0, 1]", nm[g]);
+            if (!in_range(hi[g], 3, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "sampler: %s_hi must be finite and in [0, 1]", nm[g]);
+            for (int i = 0; i < 3; i++)
+                if (lo[g][i] > hi[g][i]) return fail(LCR_ERR_INVALID, "sampler: %s_lo must not exceed %s_hi (channel %d: %g > %g)", nm[g], nm[g], i, (double)lo[g][i], (double)hi[g][i]);
+        }
+    }
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to give a look");
+    for (int k = 0; k < n_variants; k++)
+        for (int c = 0; c < 2; c++) {
+            double p[3], X[3], Y[3];
+            scene_cam_pose(c, p, X, Y);
+            if (p[2] + (double)variants[k].cam_dpos[c][2] < 0.05)
+                return fail(LCR_ERR_INVALID, "variant %d: cam_dpos leaves camera %d %.3f m above the floor, less than 0.05 m", k, c, p[2] + (double)variants[k].cam_dpos[c][2]);
+        }
+    if (s->look_K) {
+        const bool same = s->look_K == n_variants && memcmp(s->look_variants, variants, sizeof(lcr_look_variant) * n_variants) == 0 && s->look_has_sampler == (sampler != nullptr) &&
+                          (!sampler || (sampler->seed == s->look_sampler.seed && memcmp(sampler->cube_lo, s->look_sampler.cube_lo, sizeof(float) * 18) == 0));
+        if (same) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "a look of %d variants is enabled already and fixed for the life of the handle", s->look_K);
+    }
+    if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the look first and the planes second (their cached backgrounds are drawn per variant)");
+
+    const size_t N = (size_t)s->dev.n, img = (size_t)s->dev.img_h * s->dev.img_w * 3, K = (size_t)n_variants;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    const size_t o_var = off; off += al(sizeof(LcrLookVar) * K);
+    const size_t o_bg = off; off += al(K * 2 * img);
+    const size_t o_cur = off; off += al(sizeof(int) * 10 * N);
+    const size_t o_term = off; off += al(sizeof(int) * 10 * N);
+    const size_t o_ep = off; off += al(sizeof(unsigned) * N);
+    size_t o_snap[2] = {off, off};
+    if (s->rstream) for (int p = 0; p < 2; p++) { o_snap[p] = off; off += al(sizeof(int) * 10 * N); }
+    lcr_look_variant *copy = (lcr_look_variant *)malloc(sizeof(lcr_look_variant) * K);
+    if (!copy) return fail(LCR_ERR_OOM, "host allocation failed");
+    memcpy(copy, variants, sizeof(lcr_look_variant) * K);
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) { free(copy); return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the look failed: %s", off, hipGetErrorString(e)); }
+    char *base = (char *)mem;
+    // the variant table as the kernels read it: cameras in fp64 as the scene cameras are built
+    std::vector<LcrLookVar> tab(K);
+    for (size_t k = 0; k < K; k++) {
+        const lcr_look_variant &v = variants[k];
+        LcrLookVar &t = tab[k];
+        memset(&t, 0, sizeof t);
+        for (int c = 0; c < 2; c++) make_look_camera(v, c, s->dev.img_h, t.cam[c]);
+        t.ambient = v.ambient; t.diffuse = v.diffuse;
+        memcpy(t.floor_rgb, v.floor_rgb, sizeof t.floor_rgb);
+        memcpy(t.sky_rgb, v.sky_rgb, sizeof t.sky_rgb); memcpy(t.sky_slope, v.sky_slope, sizeof t.sky_slope);
+        memcpy(t.arm_rgb, v.arm_rgb, sizeof t.arm_rgb); memcpy(t.finger_rgb, v.finger_rgb, sizeof t.finger_rgb);
+    }
+    // every env: variant 0 and its task's colours
+    std::vector<int> init(10 * N, 0);
+    for (int j = 0; j < 9; j++) {
+        int bits;
+        memcpy(&bits, &LOOK_TASK_RGB[j], sizeof bits);
+        for (size_t i = 0; i < N; i++) init[(size_t)(1 + j) * N + i] = bits;
+    }
+    LcrLookSampler SM;
+    memset(&SM, 0, sizeof SM);
+    SM.K = n_variants;
+    if (sampler) {
+        SM.on = 1; SM.seed = sampler->seed;
+        const float *lo[3] = {sampler->cube_lo, sampler->cube2_lo, sampler->marker_lo}, *hi[3] = {sampler->cube_hi, sampler->cube2_hi, sampler->marker_hi};
+        for (int j = 0; j < 9; j++) { SM.lo[j] = lo[j / 3][j % 3]; SM.hi[j] = hi[j / 3][j % 3]; SM.rng[j] = SM.hi[j] - SM.lo[j]; }
+    }
+    LcrLook LK;
+    LK.var = (const LcrLookVar *)(base + o_var);
+    LK.bg = (const unsigned char *)(base + o_bg);
+    LK.variant = (const int *)(base + o_cur);
+    LK.rgb = (const float *)(base + o_cur) + N;
+    int rc = (int)hipStreamSynchronize(s->stream);
+    if (!rc) rc = (int)hipMemset(mem, 0, off);
+    if (!rc) rc = (int)hipMemcpy(base + o_var, tab.data(), sizeof(LcrLookVar) * K, hipMemcpyHostToDevice);
+    if (!rc) rc = (int)hipMemcpy(base + o_cur, init.data(), sizeof(int) * 10 * N, hipMemcpyHostToDevice);
+    if (!rc) rc = (int)hipMemcpy(base + o_term, init.data(), sizeof(int) * 10 * N, hipMemcpyHostToDevice);
+    if (!rc && sampler) rc = lcr_launch_look_redraw(s->dev.n, s->dev.env_off, nullptr, 1, SM, (int *)(base + o_cur), (unsigned *)(base + o_ep), nullptr, s->stream);
+    if (!rc) rc = lcr_launch_render_bg_look(s->dev, LK, n_variants, s->stream);
+    if (!rc) rc = lcr_launch_render_obs_look(s->dev, LK, nullptr, s->stream);
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); free(copy); return fail(LCR_ERR_HIP, "drawing the look failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->look = LK;
+    s->look_mem = mem;
+    s->look_cur = (int *)(base + o_cur);
+    s->look_term = (int *)(base + o_term);
+    s->look_episode = (unsigned *)(base + o_ep);
+    for (int p = 0; p < 2; p++) s->snap_look[p] = s->rstream ? (int *)(base + o_snap[p]) : nullptr;
+    s->look_sm = SM;
+    s->look_variants = copy;
+    s->look_has_sampler = sampler != nullptr;
+    if (sampler) s->look_sampler = *sampler;
+    s->look_K = n_variants;
+    return LCR_OK;
+}
+
+int lcr_set_look(lcr_sim *s, const uint8_t *mask_host, const int32_t *variant_host, const float *rgb_host) {
+    SIMCHK(s);
+    if (!s->look_K) return fail(LCR_ERR_INVALID, "no look is enabled on this sim (lcr_enable_look)");
+    const size_t N = (size_t)s->dev.n;
+    for (size_t i = 0; i < N; i++) {
+        if (mask_host && !mask_host[i]) continue;
+        if (variant_host && (variant_host[i] < 0 || variant_host[i] >= s->look_K)) return fail(LCR_ERR_INVALID, "variant of env %zu is %d, outside 0 .. %d", i, variant_host[i], s->look_K - 1);
+        if (rgb_host)
+            for (int j = 0; j < 9; j++)
+                if (!in_range(rgb_host + (size_t)j * N + i, 1, 0.f, 1.f)) return fail(LCR_ERR_INVALID, "rgb channel %d of env %zu must be finite and in [0, 1]", j, i);
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    std::vector<int> cur(10 * N);
+    HIPCHK(hipMemcpy(cur.data(), s->look_cur, sizeof(int) * 10 * N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; i++) {
+        if (mask_host && !mask_host[i]) continue;
+        if (variant_host) cur[i] = variant_host[i];
+        if (rgb_host)
+            for (int j = 0; j < 9; j++) memcpy(&cur[(size_t)(1 + j) * N + i], rgb_host + (size_t)j * N + i, sizeof(float));
+    }
+    HIPCHK(hipMemcpy(s->look_cur, cur.data(), sizeof(int) * 10 * N, hipMemcpyHostToDevice));
+    int rc = launch_frames(s, s->dev, s->stream);
+    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return LCR_OK;
+}
+
+int lcr_get_look(lcr_sim *s, int32_t *variant, float *rgb, uint32_t *episode) {
+    SIMCHK(s);
+    if (!s->look_K) return fail(LCR_ERR_INVALID, "no look is enabled on this sim (lcr_enable_look)");
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const size_t N = (size_t)s->dev.n;
+    if (variant) HIPCHK(hipMemcpy(variant, s->look_cur, sizeof(int) * N, hipMemcpyDeviceToHost));
+    if (rgb) HIPCHK(hipMemcpy(rgb, s->look_cur + N, sizeof(float) * 9 * N, hipMemcpyDeviceToHost));
+    if (episode) HIPCHK(hipMemcpy(episode, s->look_episode, sizeof(unsigned) * N, hipMemcpyDeviceToHost));
     return LCR_OK;
 }
 

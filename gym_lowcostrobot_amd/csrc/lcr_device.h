@@ -94,6 +94,28 @@ struct LcrPlanes {
     float far;
 };
 
+// the look of the image observations (lcr_enable_look).  One variant: everything the cached background depends on -- the two observation cameras, floor, sky, light, the arm's colours
+struct LcrLookVar {
+    LcrCam cam[2];                         // camera_front, camera_top of this variant (s = 2 tan(fovy / 2) / img_h)
+    float ambient, diffuse, _pad[2];       // (16 floats from cam[1] on: what a wave of the frame kernel fetches with one load)
+    float floor_rgb[2][3];                 // checker cells: odd, even
+    float sky_rgb[3], sky_slope[3];
+    float arm_rgb[3], finger_rgb[3];
+};
+// A kernel argument of its own, as LcrPlanes is: LcrDev and every kernel that draws without a look stay as they are
+struct LcrLook {
+    const LcrLookVar *var;                 // [K]
+    const unsigned char *bg;               // [K][2][img_h][img_w][3] cached backgrounds, one pair per variant
+    const int *variant;                    // [n] variant of every env
+    const float *rgb;                      // [9][n] cube, second cube, target marker
+};
+// the sampler of lcr_enable_look as the redraw kernel takes it
+struct LcrLookSampler {
+    unsigned long long seed;
+    float lo[9], rng[9], hi[9];            // cube, second cube, marker: value = min(lo + u rng, hi)
+    int on, K;
+};
+
 // launchers implemented in lcr_kernels.hip / lcr_render.hip (plain C++ linkage, same shared object)
 int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
 // the Newton kernels of the faithful preset (lcr_kernels.hip, unit LCR_PART = 4)
@@ -118,3 +140,12 @@ int lcr_launch_render_obs_planes(const LcrDev &P, const LcrCam &front, const Lcr
 int lcr_launch_render_bg_planes(const LcrDev &P, const LcrCam &front, const LcrCam &top, const LcrPlanes &PL, void *stream);
 int lcr_launch_render_single_planes(const LcrDev &P, const LcrCam &cam, int env, int W, int H, float far, float *depth_dev, unsigned char *seg_dev, void *stream);
 int lcr_launch_calib_copy(const float *src, float *dst, size_t n, void *stream);
+// the look (lcr_render.hip, unit LCR_RENDER_PART = 4): frames (+ planes when PL is given) / the K cached backgrounds / their planes / one env, one ray per pixel /
+// the redraw of the envs a step or a reset has reset / the gather of the terminal looks of listed envs
+int lcr_launch_render_obs_look(const LcrDev &P, const LcrLook &LK, const LcrPlanes *PL, void *stream);
+int lcr_launch_render_bg_look(const LcrDev &P, const LcrLook &LK, int K, void *stream);
+int lcr_launch_render_bg_planes_look(const LcrDev &P, const LcrLook &LK, int K, const LcrPlanes &PL, void *stream);
+int lcr_launch_render_single_look(const LcrDev &P, const LcrCam &cam, int env, int W, int H, unsigned char *out_dev, const LcrLook &LK, int look_env, int look_n, void *stream);
+// mode 0: envs with flag[e] != 0 (null: all) count an episode and draw its look, `term` (or null) receives the look they had; 1: every env draws the look of episode 0
+int lcr_launch_look_redraw(int n, long long env_off, const unsigned char *flag, int mode, const LcrLookSampler &SM, int *cur, unsigned *episode, int *term, void *stream);
+int lcr_launch_look_gather(const int *ids_dev, int count, int n, const int *look, int *out, void *stream);

@@ -22,14 +22,16 @@
 
 using namespace lcrdev;
 
-// This file is compiled as three units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes, 3 = the
-// kernels that draw the depth / segmentation planes (include/lcr.h: lcr_enable_image_planes); undefined = everything in one unit (the tools that compile this file on its own)
+// This file is compiled as four units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes, 3 = the
+// kernels that draw the depth / segmentation planes (include/lcr.h: lcr_enable_image_planes), 4 = the kernels that draw with a look (lcr_enable_look); undefined = everything in
+// one unit (the tools that compile this file on its own)
 #ifndef LCR_RENDER_PART
 #define LCR_RENDER_PART 2
 #endif
 #define LCR_RENDER_SMALL (LCR_RENDER_PART == 0 || LCR_RENDER_PART == 2)
 #define LCR_RENDER_SIZED (LCR_RENDER_PART == 1 || LCR_RENDER_PART == 2)
 #define LCR_RENDER_PLANES (LCR_RENDER_PART == 3 || LCR_RENDER_PART == 2)
+#define LCR_RENDER_LOOK (LCR_RENDER_PART == 4 || LCR_RENDER_PART == 2)
 
 namespace {
 
@@ -198,37 +200,50 @@ DEV bool box_hit(const float *c, float sx, float sy, float tlimit, float &tmin, 
     return tmin <= tmax && tmin > 0.f && tmin < tlimit;
 }
 
-#if LCR_RENDER_SMALL   // (the per-pixel shading of the background and single-frame kernels)
-DEV f3 floor_or_sky(f3 ro, f3 d, float inv_len, float &tfloor) {
+// what a look variant changes in the shading (include/lcr.h: lcr_look_variant); the values every build without a look draws with
+struct Shade {
+    f3 floor_odd, floor_even, sky, sky_slope;
+    float amb, dif;   // ambient + headlight (reach_cube.xml:8)
+};
+[[maybe_unused]] DEV Shade default_shade() {
+    Shade h;
+    h.floor_odd = mk(0.2f, 0.3f, 0.4f); h.floor_even = mk(0.1f, 0.2f, 0.3f);
+    h.sky = mk(0.15f, 0.25f, 0.35f); h.sky_slope = mk(0.15f, 0.25f, 0.35f);
+    h.amb = 0.3f; h.dif = 0.6f;
+    return h;
+}
+
+#if LCR_RENDER_SMALL || LCR_RENDER_LOOK   // (the per-pixel shading of the background and single-frame kernels)
+DEV f3 floor_or_sky(f3 ro, f3 d, float inv_len, float &tfloor, const Shade &h) {
     // checker floor below the horizon (builtin checker, 0.1 m squares; its normal is +z so the Lambert term is -d_z / |d|), gradient sky above (unshaded)
     const float rdz = d.z * inv_len;
     if (rdz < -1e-6f) {
         tfloor = -ro.z * rcp(d.z);
         const float fx = fmaf(tfloor, d.x, ro.x), fy = fmaf(tfloor, d.y, ro.y);
         const int cell = ((int)floorf(fx * 10.f) + (int)floorf(fy * 10.f)) & 1;
-        const float lam = fminf(fmaf(-0.6f, rdz, 0.3f), 1.f);
-        return lam * (cell ? mk(0.2f, 0.3f, 0.4f) : mk(0.1f, 0.2f, 0.3f));
+        const float lam = fminf(fmaf(-h.dif, rdz, h.amb), 1.f);
+        return lam * (cell ? h.floor_odd : h.floor_even);
     }
     tfloor = 1e30f;
     const float a = clampf(rdz * 2.f, 0.f, 1.f);
-    return mk(0.15f + a * 0.15f, 0.25f + a * 0.25f, 0.35f + a * 0.35f);
+    return mk(h.sky.x + a * h.sky_slope.x, h.sky.y + a * h.sky_slope.y, h.sky.z + a * h.sky_slope.z);
 }
 
 // one pixel, every primitive of the scene (cached background: the base only; render(): all): linear rgb in [0,1]
-DEV f3 shade_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, int nbox, int marker, float sx, float sy) {
+DEV f3 shade_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, int nbox, int marker, float sx, float sy, const Shade &h) {
     const f3 ro = mk(C.px, C.py, C.pz);
     const f3 d = mk(C.xx * sx + C.yx * sy - C.zx, C.xy * sx + C.yy * sy - C.zy, C.xz * sx + C.yz * sy - C.zz);
     const float inv_len = rsq(dot(d, d));
     float tbest;
-    f3 out = floor_or_sky(ro, d, inv_len, tbest);
+    f3 out = floor_or_sky(ro, d, inv_len, tbest, h);
     float talpha = 0.f, tlamd = 0.f;
     for (int k = 0; k < nbox; k++) {
         float tmin, ld;
         if (!box_hit(boxc[k], sx, sy, tbest, tmin, ld)) continue;
         if (k == marker) { tlamd = ld; talpha = boxc[k][15]; }
-        else { tbest = tmin; out = fminf(fmaf(0.6f * inv_len, ld, 0.3f), 1.f) * bcol[k]; }
+        else { tbest = tmin; out = fminf(fmaf(h.dif * inv_len, ld, h.amb), 1.f) * bcol[k]; }
     }
-    if (talpha > 0.f) out = axpy(talpha * fmaf(0.6f * inv_len, tlamd, 0.3f), bcol[marker], (1.f - talpha) * out);
+    if (talpha > 0.f) out = axpy(talpha * fmaf(h.dif * inv_len, tlamd, h.amb), bcol[marker], (1.f - talpha) * out);
     return out;
 }
 
@@ -240,7 +255,7 @@ DEV f3 shade_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, int
 // tnear its ray parameter (1e30: sky), knear its box (-1: floor or sky), mhit whether the translucent marker lies in front of it -- whatever the return value.
 template <bool PLANES>
 DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float sy, f3 d, unsigned m, const unsigned char *stpx, unsigned &rgb, float &tnear, int &knear,
-                    bool &mhit) {
+                    bool &mhit, float amb, float dif) {
     float tbest = d.z < -1e-6f ? -ro.z * rcp(d.z) : 1e30f;   // the floor hides what lies below it
     int kbest = -1;
     float lamd = 0.f;   // |n . d| of the nearest hit
@@ -257,11 +272,11 @@ DEV bool shade_span(const Scene &S, int cam, int marker, f3 ro, float sx, float 
     const bool draw = kbest > BASE || talpha > 0.f;   // (a pixel whose nearest hit is the base keeps its background bytes)
     if (!__any(draw)) return false;
     const float inv_len = rsq(dot(d, d));
-    const float lam = fminf(fmaf(0.6f * inv_len, lamd, 0.3f), 1.f);  // ambient + headlight (reach_cube.xml:8)
+    const float lam = fminf(fmaf(dif * inv_len, lamd, amb), 1.f);  // ambient + headlight (reach_cube.xml:8)
     f3 out = lam * S.bcol[kbest < 0 ? 0 : kbest];
     if (__any(talpha > 0.f)) {   // the translucent marker: over the opaque hit, or over the staged background
         if (kbest <= BASE) out = mk(stpx[0] * (1.f / 255.f), stpx[1] * (1.f / 255.f), stpx[2] * (1.f / 255.f));
-        const float tl = fmaf(0.6f * inv_len, tlamd, 0.3f);
+        const float tl = fmaf(dif * inv_len, tlamd, amb);
         if (talpha > 0.f) out = axpy(talpha * tl, S.bcol[marker < 0 ? 0 : marker], (1.f - talpha) * out);
     }
     rgb = pack_rgb(out);
@@ -285,7 +300,7 @@ __global__ __launch_bounds__(256) void lcr_render_bg_kernel(LcrDev P, LcrCam fro
     float boxc[1][16];
     box_consts(C, bc, bX, bY, bZ, bh, 1.f, boxc[0]);
     const f3 col = mk(0.8f, 0.8f, 0.8f);
-    const unsigned rgb = pack_rgb(shade_pixel(C, boxc, &col, 1, -1, sx, sy));
+    const unsigned rgb = pack_rgb(shade_pixel(C, boxc, &col, 1, -1, sx, sy, default_shade()));
     P.img_bg[3 * (size_t)pix + 0] = (unsigned char)rgb;
     P.img_bg[3 * (size_t)pix + 1] = (unsigned char)(rgb >> 8);
     P.img_bg[3 * (size_t)pix + 2] = (unsigned char)(rgb >> 16);
@@ -302,9 +317,27 @@ DEV unsigned or_row0(unsigned x) {
     return (unsigned)__builtin_amdgcn_readlane((int)x, 15);
 }
 
-// the optional fourth argument of the frame kernel (a parameter pack of at most one LcrPlanes)
-[[maybe_unused]] DEV LcrPlanes planes_arg() { return LcrPlanes{}; }
-[[maybe_unused]] DEV LcrPlanes planes_arg(const LcrPlanes &pl) { return pl; }
+// the optional arguments of the frame kernel behind the cameras (a parameter pack: nothing, LcrPlanes, LcrLook, or LcrLook and LcrPlanes): the one of type T, or an empty T
+template <typename T>
+[[maybe_unused]] DEV T pack_arg() { return T{}; }
+template <typename T, typename A, typename... R>
+[[maybe_unused]] DEV T pack_arg(const A &a, const R &...r) {
+    if constexpr (std::is_same<T, A>::value) return a;
+    else return pack_arg<T>(r...);
+}
+template <typename T, typename... A>
+constexpr bool pack_has() { return (std::is_same<T, A>::value || ... || false); }
+
+// LOOK builds: the env's colours over what build_scene drew -- the arm in the variant's colours, cube, second cube and marker in the env's own
+[[maybe_unused]] DEV void apply_look(const LcrLook &LK, const LcrLookVar &V, int env, int n, int task, int has_target, f3 *bcol) {
+    const f3 arm = mk(V.arm_rgb[0], V.arm_rgb[1], V.arm_rgb[2]), finger = mk(V.finger_rgb[0], V.finger_rgb[1], V.finger_rgb[2]);
+    for (int i = 0; i < NARM; i++) bcol[i] = i >= 5 ? finger : arm;
+    const float *c = LK.rgb + env;
+    int nb = NARM;
+    bcol[nb++] = mk(c[0], c[n], c[2 * (size_t)n]);
+    if (task == 4) bcol[nb++] = mk(c[3 * (size_t)n], c[4 * (size_t)n], c[5 * (size_t)n]);
+    if (has_target) bcol[nb] = mk(c[6 * (size_t)n], c[7 * (size_t)n], c[8 * (size_t)n]);
+}
 
 // COUNT: diagnostics build (LCR_RENDER_COUNT=1 and lcr_config.diagnostics): ray-cast passes / primitive tests / pixels written per env into
 // active_count / choice / max_sweeps (tools/render_work.py)
@@ -317,15 +350,22 @@ DEV unsigned or_row0(unsigned x) {
 // EPW = envs per workgroup (1, 2, 4), the mapping for small frames: 4 / EPW waves per env -- 4: two per camera, alternate bands; 2: one per camera; 1: one wave draws
 // both frames of its env -- so that the scene set-up of EPW envs runs side by side and a workgroup lives EPW times longer against its launch.
 //
-// PLANES (a fourth kernel argument, LcrPlanes, is given -- `PLS` is empty or that one type, so the colour-only builds keep their signature; run-time sizes only): the enabled
+// PLANES (a kernel argument of type LcrPlanes is given -- `PLS` is empty, LcrPlanes, LcrLook or both, so the colour-only builds keep their signature; run-time sizes only): the enabled
 // depth / segmentation planes of PL are drawn beside the colours.  A band no silhouette touches copies the cached background bands (16 W B of depth, 4 W B of segmentation)
 // with 16-B stores.  In a touched band the segmentation band is staged in LDS behind the colours (4 W B more per wave) and leaves as 16-B stores; the depth band is NOT
 // staged -- 16 W B per wave would more than double the workgroup's LDS and leave three of the six workgroups of a CU at 320 wide -- but leaves straight from registers: the
 // ray-cast tiles store their 16 x 4 floats (64 B per row), the 16-B vectors of every other tile are copied from the background.  No byte of a plane is written twice.
+//
+// LOOK (a kernel argument of type LcrLook is given; run-time sizes only; include/lcr.h: lcr_enable_look): the env's variant index is wave-uniform.  Through it come the two cameras
+// (build_prim receives them: the culling records and boxc stay per camera as they are), the light (one 15-float load per wave and camera, read back into scalar registers) and the
+// cached background the untouched bands are copied from -- still plain 16-B copies, from one of K pairs -- and, with PLANES, the background planes of that variant's cameras.  The
+// colours of the boxes are replaced right after build_scene (apply_look).  Same expressions as the builds without a look, with values where the constants were: the default variant
+// with the task's colours draws the very bytes.
 template <bool COUNT, int NV, int EPW, int TW, int TH, typename... PLS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 : 6, NV > 4 ? 5 : 6))) void lcr_render_obs_kernel(LcrDev P, LcrCam front, LcrCam top, PLS... pls) {
-    constexpr bool PLANES = sizeof...(PLS) != 0;
-    const LcrPlanes PL = planes_arg(pls...);
+    constexpr bool PLANES = pack_has<LcrPlanes, PLS...>(), LOOK = pack_has<LcrLook, PLS...>();
+    const LcrPlanes PL = pack_arg<LcrPlanes>(pls...);
+    [[maybe_unused]] const LcrLook LK = pack_arg<LcrLook>(pls...);
     // A workgroup owns EPW envs (one: 2 H rows, front frame then top frame); a wave handles one BAND of 4 rows at a time (12 W B = 3 W / 4 lanes x
     // 16 B; 3 840 B = 240 lanes at 320 wide).  The band starts as a copy of the cached background band (L2 hit); if no primitive's silhouette touches
     // it (wave-uniform) it leaves straight away as non-temporal 16-B stores.  Otherwise the band is
@@ -338,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     constexpr bool FIXED = TW != 0;
     static_assert(!FIXED || (TW % 16 == 0 && TH % 4 == 0 && (3 * TW / 4 + 63) / 64 == NV), "a fixed size has whole tile columns and its own NV");
     static_assert(EPW == 1 || EPW == 2 || EPW == 4, "1, 2 or 4 waves per env");
-    static_assert(!PLANES || (!FIXED && !COUNT), "the planes build takes its size at run time and counts nothing");
+    static_assert(!(PLANES || LOOK) || (!FIXED && !COUNT), "the planes and look builds take their size at run time and count nothing");
     const int W = FIXED ? TW : P.img_w, H = FIXED ? TH : P.img_h;
     const int NT = (W + 15) >> 4;   // 16-pixel tile columns, the last one partial when W % 16 != 0 (<= 32: one mask word)
     const int VB = 3 * W / 4;       // 16-B vectors of a band
@@ -354,11 +394,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     const bool live = env < P.n;   // (a ragged batch: the waves of the missing envs only keep the barriers company)
     Scene &S = S_[e];
     const int tl = EPW == 1 ? (int)threadIdx.x : (int)threadIdx.x & (64 * WPE - 1);   // thread within its env's waves
-    if (tl == 0 && live) build_scene(P, env, S);
+    // LOOK: the env's variant (wave-uniform: its cameras, light and background) and colours
+    [[maybe_unused]] const LcrLookVar *LV = nullptr;
+    [[maybe_unused]] int variant = 0;
+    if (LOOK && live) { variant = __builtin_amdgcn_readfirstlane(LK.variant[env]); LV = LK.var + variant; }
+    if (tl == 0 && live) {
+        build_scene(P, env, S);
+        if (LOOK) apply_look(LK, *LV, env, P.n, P.task, P.has_target, S.bcol);
+    }
     __syncthreads();
     if (tl < 2 * NPRIM && live) {
         const int cam_id = tl / NPRIM, prim = tl - cam_id * NPRIM;
-        build_prim(cam_id ? top : front, cam_id, W, H, S, prim);
+        build_prim(LOOK ? LV->cam[cam_id] : (cam_id ? top : front), cam_id, W, H, S, prim);
     }
     __syncthreads();
     if (!live) return;
@@ -377,12 +424,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     constexpr int CAM_STEP = WPE >= 2 ? 2 : 1, BAND_STEP = WPE == 4 ? 2 : 1;
     int cam = WPE == 4 ? wsub >> 1 : (WPE == 2 ? wsub : 0);
     do {
-    const LcrCam &C = cam ? top : front;
+    // LOOK: the variant's camera and light, one load per wave and camera (lanes 0 .. 12 the camera, 13 / 14 ambient / diffuse), then wave-uniform values
+    [[maybe_unused]] LcrCam CL;
+    float amb = 0.3f, dif = 0.6f;
+    if (LOOK) {
+        const float *vf = reinterpret_cast<const float *>(LV);
+        const float w = vf[lane < 13 ? 13 * cam + lane : (lane < 15 ? 13 + lane : 0)];
+        auto rl = [&](int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), i)); };
+        CL.px = rl(0); CL.py = rl(1); CL.pz = rl(2);
+        CL.xx = rl(3); CL.xy = rl(4); CL.xz = rl(5); CL.yx = rl(6); CL.yy = rl(7); CL.yz = rl(8); CL.zx = rl(9); CL.zy = rl(10); CL.zz = rl(11);
+        CL.s = rl(12); amb = rl(13); dif = rl(14);
+    }
+    const LcrCam &C = LOOK ? CL : (cam ? top : front);
     const f3 ro = mk(C.px, C.py, C.pz), CX = mk(C.xx, C.xy, C.xz), CY = mk(C.yx, C.yy, C.yz), CZ = mk(C.zx, C.zy, C.zz);
     // culling: one primitive per lane (lane k <-> primitive k).  Per band, every lane computes the pixel interval [xa, xb] its primitive can cover on the
     // band's 4 rows (arm boxes: 2D stadium silhouette, the other boxes: bounding box) -> the interval [ta, tb] of 16-pixel tile columns it touches.
     const float *cull = S.cull[cam][lane < NPRIM ? lane : 0];
-    const u32x4 *bg = reinterpret_cast<const u32x4 *>(P.img_bg) + (size_t)cam * NB * VB;
+    const int bgi = LOOK ? 2 * variant + cam : cam;   // which cached background: one pair per variant
+    const u32x4 *bg = reinterpret_cast<const u32x4 *>(LOOK ? LK.bg : P.img_bg) + (size_t)bgi * NB * VB;
     u32x4 *out = reinterpret_cast<u32x4 *>((cam ? P.img_top : P.img_front) + (size_t)env * img_bytes);
     // PLANES: this camera's planes of this env, and their background (null pointer: plane not enabled -- wave-uniform)
     const size_t plane_px = (size_t)H * W;
@@ -393,8 +452,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     if (PLANES) {
         float *dp = cam ? PL.depth_top : PL.depth_front;
         unsigned char *sp = cam ? PL.seg_top : PL.seg_front;
-        if (dp) { dplane = reinterpret_cast<f32x4 *>(dp + (size_t)env * plane_px); dbg = reinterpret_cast<const f32x4 *>(PL.bg_depth + (size_t)cam * plane_px); }
-        if (sp) { splane = reinterpret_cast<u32x4 *>(sp + (size_t)env * plane_px); sbg = reinterpret_cast<const u32x4 *>(PL.bg_seg + (size_t)cam * plane_px); }
+        if (dp) { dplane = reinterpret_cast<f32x4 *>(dp + (size_t)env * plane_px); dbg = reinterpret_cast<const f32x4 *>(PL.bg_depth + (size_t)bgi * plane_px); }
+        if (sp) { splane = reinterpret_cast<u32x4 *>(sp + (size_t)env * plane_px); sbg = reinterpret_cast<const u32x4 *>(PL.bg_seg + (size_t)bgi * plane_px); }
     }
     // the depth band b (W vectors: 4 rows of W / 4) without the vectors of the tile columns in `skip` (a tile column = 4 vectors of each row)
     auto copy_depth_band = [&](int b, unsigned skip) {
@@ -474,7 +533,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
             float tnear = 0.f;
             int knear = -1;
             bool mhit = false;
-            const bool wrote = shade_span<PLANES>(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb, tnear, knear, mhit) && (FIXED || pxt < W);
+            const bool wrote = shade_span<PLANES>(S, cam, marker, ro, sx, sy, rdu, m, stpx, rgb, tnear, knear, mhit, amb, dif) && (FIXED || pxt < W);
             if (PLANES && pxt < W) {   // every pixel of a ray-cast tile: `m` holds all that can be seen in it, the base included
                 if (dplane) __builtin_nontemporal_store(fminf(tnear, PL.far), reinterpret_cast<float *>(dplane) + (size_t)(row0 + ty) * W + px);
                 if (splane) {
@@ -506,7 +565,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NV > 4 ? 5 
     } while ((cam += CAM_STEP) < 2);
 }
 
-#if LCR_RENDER_PLANES
+#if LCR_RENDER_PLANES || LCR_RENDER_LOOK
 // one pixel, every primitive of the scene: the nearest opaque surface -- t along the un-normalised ray, which is metres along the optical axis (1e30: sky) -- and the
 // segmentation byte of include/lcr.h
 DEV void trace_pixel(const LcrCam &C, const float (*boxc)[16], int nbox, int marker, float sx, float sy, float &t, unsigned &seg) {
@@ -525,6 +584,9 @@ DEV void trace_pixel(const LcrCam &C, const float (*boxc)[16], int nbox, int mar
     t = tbest;
     seg = (kbest >= 0 ? (unsigned)kbest + 2u : (down ? 1u : 0u)) | (mhit ? 0x80u : 0u);
 }
+#endif
+
+#if LCR_RENDER_PLANES
 
 // the background planes of the two observation cameras (floor, sky, the arm's base), rendered once at lcr_enable_image_planes into PL.bg_depth / PL.bg_seg ([2][H][W])
 __global__ __launch_bounds__(256) void lcr_render_bg_planes_kernel(LcrDev P, LcrCam front, LcrCam top, LcrPlanes PL) {
@@ -580,7 +642,7 @@ __global__ __launch_bounds__(256) void lcr_render_single_kernel(LcrDev P, LcrCam
     if (pix >= W * H) return;
     const int v = pix / W, u = pix - v * W;
     const float sx = (u + 0.5f - 0.5f * W) * cam.s, sy = -(v + 0.5f - 0.5f * H) * cam.s;
-    const unsigned rgb = pack_rgb(shade_pixel(cam, S.boxc[0], S.bcol, S.nbox, S.marker, sx, sy));
+    const unsigned rgb = pack_rgb(shade_pixel(cam, S.boxc[0], S.bcol, S.nbox, S.marker, sx, sy, default_shade()));
     out[3 * (size_t)pix + 0] = (unsigned char)rgb;
     out[3 * (size_t)pix + 1] = (unsigned char)(rgb >> 8);
     out[3 * (size_t)pix + 2] = (unsigned char)(rgb >> 16);
@@ -604,6 +666,133 @@ __global__ __launch_bounds__(256) void lcr_gather_terminal_kernel(LcrDev P, cons
     for (int j = 0; j < 3; j++) target_out[j * C + i] = P.has_target ? t[(15 + j) * N] : 0.f;
 }
 
+#endif
+
+#if LCR_RENDER_LOOK
+// ---- the look (include/lcr.h: lcr_enable_look) ----
+DEV Shade look_shade(const LcrLookVar &V) {
+    Shade h;
+    h.floor_odd = mk(V.floor_rgb[0][0], V.floor_rgb[0][1], V.floor_rgb[0][2]); h.floor_even = mk(V.floor_rgb[1][0], V.floor_rgb[1][1], V.floor_rgb[1][2]);
+    h.sky = mk(V.sky_rgb[0], V.sky_rgb[1], V.sky_rgb[2]); h.sky_slope = mk(V.sky_slope[0], V.sky_slope[1], V.sky_slope[2]);
+    h.amb = V.ambient; h.dif = V.diffuse;
+    return h;
+}
+
+// the cached backgrounds of the K variants, LK.bg [K][2][H][W][3]: lcr_render_bg_kernel with each variant's cameras, colours and light
+__global__ __launch_bounds__(256) void lcr_render_bg_look_kernel(LcrDev P, LcrLook LK, int K) {
+    const int W = P.img_w, H = P.img_h, per = 2 * W * H;
+    const int gpix = blockIdx.x * blockDim.x + threadIdx.x;   // (K <= 64 pairs of at most 512 x 512: below 2^26)
+    if (gpix >= K * per) return;
+    const int k = gpix / per, pix = gpix - k * per;
+    const LcrLookVar &V = LK.var[k];
+    const bool is_top = pix >= W * H;
+    const int p = is_top ? pix - W * H : pix;
+    const int row = p / W, px = p - row * W;
+    const LcrCam C = V.cam[is_top ? 1 : 0];
+    const float sy = -(row + 0.5f - 0.5f * H) * C.s, sx = (px + 0.5f - 0.5f * W) * C.s;
+    f3 bc, bX, bY, bZ, bh;
+    base_box(bc, bX, bY, bZ, bh);
+    float boxc[1][16];
+    box_consts(C, bc, bX, bY, bZ, bh, 1.f, boxc[0]);
+    const f3 col = mk(V.arm_rgb[0], V.arm_rgb[1], V.arm_rgb[2]);
+    const unsigned rgb = pack_rgb(shade_pixel(C, boxc, &col, 1, -1, sx, sy, look_shade(V)));
+    unsigned char *o = const_cast<unsigned char *>(LK.bg) + 3 * (size_t)gpix;
+    o[0] = (unsigned char)rgb; o[1] = (unsigned char)(rgb >> 8); o[2] = (unsigned char)(rgb >> 16);
+}
+
+// their planes, PL.bg_depth / PL.bg_seg [K][2][H][W]
+__global__ __launch_bounds__(256) void lcr_render_bg_planes_look_kernel(LcrDev P, LcrLook LK, int K, LcrPlanes PL) {
+    const int W = P.img_w, H = P.img_h, per = 2 * W * H;
+    const int gpix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gpix >= K * per) return;
+    const int k = gpix / per, pix = gpix - k * per;
+    const bool is_top = pix >= W * H;
+    const int p = is_top ? pix - W * H : pix;
+    const int row = p / W, px = p - row * W;
+    const LcrCam C = LK.var[k].cam[is_top ? 1 : 0];
+    const float sy = -(row + 0.5f - 0.5f * H) * C.s, sx = (px + 0.5f - 0.5f * W) * C.s;
+    f3 bc, bX, bY, bZ, bh;
+    base_box(bc, bX, bY, bZ, bh);
+    float boxc[1][16];
+    box_consts(C, bc, bX, bY, bZ, bh, 1.f, boxc[0]);
+    float t;
+    unsigned seg;
+    trace_pixel(C, boxc, 1, -1, sx, sy, t, seg);
+    PL.bg_depth[gpix] = fminf(t, PL.far);
+    PL.bg_seg[gpix] = (unsigned char)seg;
+}
+
+// lcr_render_single_kernel with the look of env `look_env` of LK (its variant's colours and light, its own colours); the camera is the caller's
+__global__ __launch_bounds__(256) void lcr_render_single_look_kernel(LcrDev P, LcrCam cam, int env, int W, int H, unsigned char *out, LcrLook LK, int look_env, int look_n) {
+    __shared__ Scene S;
+    const LcrLookVar &V = LK.var[LK.variant[look_env]];
+    if (threadIdx.x == 0) {
+        build_scene(P, env, S);
+        apply_look(LK, V, look_env, look_n, P.task, P.has_target, S.bcol);
+    }
+    __syncthreads();
+    if (threadIdx.x < NBOX && (int)threadIdx.x < S.nbox)
+        box_consts(cam, S.bc[threadIdx.x], S.bX[threadIdx.x], S.bY[threadIdx.x], S.bZ[threadIdx.x], S.bh[threadIdx.x], S.balpha[threadIdx.x], S.boxc[0][threadIdx.x]);
+    __syncthreads();
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= W * H) return;
+    const int v = pix / W, u = pix - v * W;
+    const float sx = (u + 0.5f - 0.5f * W) * cam.s, sy = -(v + 0.5f - 0.5f * H) * cam.s;
+    const unsigned rgb = pack_rgb(shade_pixel(cam, S.boxc[0], S.bcol, S.nbox, S.marker, sx, sy, look_shade(V)));
+    out[3 * (size_t)pix + 0] = (unsigned char)rgb;
+    out[3 * (size_t)pix + 1] = (unsigned char)(rgb >> 8);
+    out[3 * (size_t)pix + 2] = (unsigned char)(rgb >> 16);
+}
+
+// Philox-4x32-10 (the generator of lcr_fill_random_actions): key = seed, counter = (global env id, episode, block)
+DEV void look_philox(unsigned long long seed, unsigned long long gid, uint32_t episode, uint32_t blk, uint32_t (&c)[4]) {
+    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    c[0] = (uint32_t)gid; c[1] = (uint32_t)(gid >> 32); c[2] = episode; c[3] = blk;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0], hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// The look of the envs that were reset (include/lcr.h: the sampler).  `cur` / `term`: [10][n] words, row 0 the variant, rows 1 .. 9 the colours (float bits).
+// mode 0: envs with flag[e] != 0 (flag null: all) hand their look to `term` (when given), count an episode and -- with a sampler -- draw that episode's look;
+// mode 1: every env draws the look of episode 0 (lcr_enable_look)
+__global__ __launch_bounds__(256) void lcr_look_redraw_kernel(int n, long long env_off, const unsigned char *flag, int mode, LcrLookSampler SM, int *cur, unsigned *episode, int *term) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    uint32_t ep = 0;
+    if (mode == 0) {
+        if (flag && !flag[e]) return;
+        if (term)
+            for (int j = 0; j < 10; j++) term[(size_t)j * n + e] = cur[(size_t)j * n + e];
+        ep = episode[e] + 1u;
+        episode[e] = ep;
+    }
+    if (!SM.on) return;
+    const unsigned long long gid = (unsigned long long)(env_off + e);
+    uint32_t w[12];
+    for (uint32_t b = 0; b < 3; b++) {
+        uint32_t c[4];
+        look_philox(SM.seed, gid, ep, b, c);
+        for (int i = 0; i < 4; i++) w[4 * b + i] = c[i];
+    }
+    cur[e] = (int)__umulhi(w[0], (uint32_t)SM.K);
+    for (int j = 0; j < 9; j++) {
+        const float u = (float)(w[1 + j] >> 8) * (1.0f / 16777216.0f);
+        cur[(size_t)(1 + j) * n + e] = __float_as_int(fminf(fmaf(u, SM.rng[j], SM.lo[j]), SM.hi[j]));
+    }
+}
+
+// the looks of the listed envs as a compact [10][count] block (lcr_render_terminal: the terminal looks)
+__global__ __launch_bounds__(256) void lcr_look_gather_kernel(const int *ids, int count, int n, const int *look, int *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const int e = ids[i];
+    for (int j = 0; j < 10; j++) out[(size_t)j * count + i] = look[(size_t)j * n + e];
+}
 #endif
 
 }  // namespace
@@ -679,6 +868,67 @@ int lcr_launch_render_bg_planes(const LcrDev &P, const LcrCam &front, const LcrC
 
 int lcr_launch_render_single_planes(const LcrDev &P, const LcrCam &cam, int env, int W, int H, float far, float *depth_dev, unsigned char *seg_dev, void *stream) {
     hipLaunchKernelGGL(lcr_render_single_planes_kernel, dim3((W * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, cam, env, W, H, far, depth_dev, seg_dev);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+#endif
+
+#if LCR_RENDER_LOOK
+namespace {
+template <int NV, int EPW>
+void launch_obs_look(const LcrDev &P, const LcrLook &LK, const LcrPlanes *PL, void *stream) {
+    const LcrCam none{};   // (the cameras come from the variants)
+    const dim3 grid((P.n + EPW - 1) / EPW);
+    if (PL) hipLaunchKernelGGL((lcr_render_obs_kernel<false, NV, EPW, 0, 0, LcrLook, LcrPlanes>), grid, dim3(256), (size_t)4 * 16 * P.img_w, (hipStream_t)stream, P, none, none, LK, *PL);
+    else hipLaunchKernelGGL((lcr_render_obs_kernel<false, NV, EPW, 0, 0, LcrLook>), grid, dim3(256), (size_t)4 * 12 * P.img_w, (hipStream_t)stream, P, none, none, LK);
+}
+}  // namespace
+
+// colour frames (+ the enabled planes when PL is given) with a look: the run-time-size builds at every size, same mappings as launch_obs_sized
+int lcr_launch_render_obs_look(const LcrDev &P, const LcrLook &LK, const LcrPlanes *PL, void *stream) {
+    if (!P.img_front || !P.img_top || !LK.var || !LK.bg || !LK.variant || !LK.rgb || (PL && (!PL->bg_depth || !PL->bg_seg))) return (int)hipErrorInvalidValue;
+    const int nv = (3 * P.img_w / 4 + 63) / 64, epw = P.img_epw;
+    if (nv > 4) launch_obs_look<6, 1>(P, LK, PL, stream);
+    else if (nv > 2) launch_obs_look<4, 1>(P, LK, PL, stream);
+    else if (nv > 1) {
+        if (epw == 4) launch_obs_look<2, 4>(P, LK, PL, stream);
+        else if (epw == 2) launch_obs_look<2, 2>(P, LK, PL, stream);
+        else launch_obs_look<2, 1>(P, LK, PL, stream);
+    } else {
+        if (epw == 4) launch_obs_look<1, 4>(P, LK, PL, stream);
+        else if (epw == 2) launch_obs_look<1, 2>(P, LK, PL, stream);
+        else launch_obs_look<1, 1>(P, LK, PL, stream);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_bg_look(const LcrDev &P, const LcrLook &LK, int K, void *stream) {
+    hipLaunchKernelGGL(lcr_render_bg_look_kernel, dim3((K * 2 * P.img_w * P.img_h + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, LK, K);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_bg_planes_look(const LcrDev &P, const LcrLook &LK, int K, const LcrPlanes &PL, void *stream) {
+    hipLaunchKernelGGL(lcr_render_bg_planes_look_kernel, dim3((K * 2 * P.img_w * P.img_h + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, LK, K, PL);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_single_look(const LcrDev &P, const LcrCam &cam, int env, int W, int H, unsigned char *out_dev, const LcrLook &LK, int look_env, int look_n, void *stream) {
+    hipLaunchKernelGGL(lcr_render_single_look_kernel, dim3((W * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, cam, env, W, H, out_dev, LK, look_env, look_n);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_look_redraw(int n, long long env_off, const unsigned char *flag, int mode, const LcrLookSampler &SM, int *cur, unsigned *episode, int *term, void *stream) {
+    hipLaunchKernelGGL(lcr_look_redraw_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, env_off, flag, mode, SM, cur, episode, term);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_look_gather(const int *ids_dev, int count, int n, const int *look, int *out, void *stream) {
+    hipLaunchKernelGGL(lcr_look_gather_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, ids_dev, count, n, look, out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

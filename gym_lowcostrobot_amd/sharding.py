@@ -62,6 +62,7 @@ class ShardedVecSim:
             raise ValueError("n_envs_total must be divisible by the number of shards")
         self.per = n_envs_total // len(devices)
         self.n = n_envs_total
+        # (look_variants / look_sampler too: the sampler is keyed by the global env id, so the shards draw the looks the whole job would)
         # (image_planes / depth_far, like every other keyword, go to each shard's VecSim: the planes are per-shard device arrays, shards[i].depth_front ...)
         # every shard declares the whole job (lcr_config.global_envs): the same kernel family on every shard, and lcr_create checks that the cut is at wave boundaries
         kw.setdefault("global_envs", n_envs_total)
@@ -87,6 +88,12 @@ class ShardedVecSim:
 
         sts = [s.get_state() for s in self.shards]
         return {k: np.concatenate([st[k] for st in sts], axis=-1) for k in sts[0]}
+
+    def look(self):
+        import numpy as np
+
+        ls = [s.look() for s in self.shards]
+        return {"variants": ls[0]["variants"], **{k: np.concatenate([l[k] for l in ls], axis=-1) for k in ("variant", "rgb", "episode")}}
 
     def outputs(self):
         import numpy as np

@@ -90,6 +90,8 @@ class VecSim:
         image_size=None,
         image_planes=(),
         depth_far=10.0,
+        look_variants=None,
+        look_sampler=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -110,6 +112,14 @@ class VecSim:
             raise ValueError(f"depth_far must be a number of metres in (0, 1000], got {depth_far!r}") from None
         if not (np.isfinite(depth_far) and 0.0 < depth_far <= 1000.0):
             raise ValueError(f"depth_far must be finite and in (0, 1000] metres, got {depth_far!r}")
+        # the look of the frames (lcr_enable_look): a list of variants (LookVariant or dicts over the default variant) and an optional sampler of the per-env colours
+        if look_sampler is not None and look_variants is None:
+            look_variants = [{}]
+        if look_variants is not None:
+            if observation_mode == "state":
+                raise ValueError("look_variants need image observations: observation_mode 'image' or 'both'")
+            look_variants = [_capi.LookVariant.from_any(v) for v in look_variants]
+            look_sampler = None if look_sampler is None else _capi.LookSampler.from_any(look_sampler)
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -206,6 +216,14 @@ class VecSim:
         img = (N,) + self.image_size + (3,)
         self.image_front = DeviceArray(self, ov.image_front, img, np.uint8) if ov.image_front else None
         self.image_top = DeviceArray(self, ov.image_top, img, np.uint8) if ov.image_top else None
+        self.look_variants, self.look_sampler = look_variants, look_sampler
+        if look_variants is not None:   # (before the planes: their cached backgrounds are drawn per variant)
+            try:
+                arr = (_capi.LookVariant * len(look_variants))(*look_variants)
+                check(self.L.lcr_enable_look(self.handle, len(look_variants), arr, None if look_sampler is None else ctypes.byref(look_sampler)))
+            except Exception:
+                self.close()
+                raise
         self.image_planes, self.depth_far = image_planes, depth_far
         self.depth_front = self.depth_top = self.seg_front = self.seg_top = None
         if image_planes:
@@ -320,6 +338,28 @@ class VecSim:
         top = np.empty_like(front)
         check(self.L.lcr_render_terminal(self.handle, _vp(ids), int(ids.size), _vp(front), _vp(top)))
         return front, top
+
+    def look(self):
+        """the looks of the envs (lcr_get_look): {"variants": the handle's list of LookVariant, "variant": (N,) int32, "rgb": (9, N) float32 -- cube, second cube, marker --,
+        "episode": (N,) uint32 resets of each env so far}.  `set_look(variant=, rgb=)` of it restores the looks."""
+        if self.look_variants is None:
+            raise ValueError("look: no look is enabled (look_variants)")
+        variant, rgb, episode = np.zeros(self.n, np.int32), np.zeros((9, self.n), np.float32), np.zeros(self.n, np.uint32)
+        check(self.L.lcr_get_look(self.handle, _vp(variant), _vp(rgb), _vp(episode)))
+        return {"variants": list(self.look_variants), "variant": variant, "rgb": rgb, "episode": episode}
+
+    def set_look(self, variant=None, rgb=None, mask=None):
+        """give the masked envs (None: all) a variant index and / or colours ((9, N): cube, second cube, marker rgb) and redraw the frames (lcr_set_look)"""
+        v = None if variant is None else np.ascontiguousarray(variant, np.int32)
+        c = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if v is not None and v.shape != (self.n,):
+            raise ValueError("variant must have shape (n_envs,)")
+        if c is not None and c.shape != (9, self.n):
+            raise ValueError("rgb must have shape (9, n_envs)")
+        if m is not None and m.shape != (self.n,):
+            raise ValueError("mask must have shape (n_envs,)")
+        check(self.L.lcr_set_look(self.handle, _vp(m), _vp(v), _vp(c)))
 
     def render_planes(self, env=0, camera="camera_front", width=320, height=240):
         """depth and segmentation of one env, one ray per pixel (the sibling of render()): ((height, width) float32 metres along the optical axis, clipped at

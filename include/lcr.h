@@ -365,6 +365,47 @@ int lcr_render_state_planes(lcr_sim *sim, int camera, int width, int height, con
  * enabled; a pointer of a plane that is not enabled may be NULL (and is not written). */
 int lcr_render_terminal_planes(lcr_sim *sim, const int32_t *env_ids_host, int count, float *depth_front, float *depth_top, uint8_t *seg_front, uint8_t *seg_top);
 
+/* == The look of the image observations: visual domain randomisation (the reference trains policies for a real arm watched by real cameras; its envs draw one fixed world).
+ * A look has two parts: a VARIANT, one of n_variants per handle, which holds everything the cached background of the frame kernel depends on -- the two observation
+ * cameras, floor, sky, light, the arm's colours -- and nine per-env colour channels (cube, second cube, target marker).  Every env points at one variant; the frame kernel
+ * copies untouched bands from that variant's background and ray-casts the rest with that variant's cameras and light and the env's colours.  Without lcr_enable_look every
+ * frame is what it was: the default variant with the task's colours (cube 0.5 0 0, second cube 0 0 0.5, marker 0 0 1) draws the very bytes of a handle without a look.
+ *   sampler  counter-based, no state of its own and none of the envs' PCG64 streams (state trajectories with and without a look are bit-identical): Philox-4x32-10, the
+ *            generator of lcr_fill_random_actions, with key (seed low word, seed high word) and counter (global env id low, high, episode count of the env, block b); the
+ *            blocks b = 0, 1, 2 give the words w[0 .. 11].  variant = (w[0] * n_variants) >> 32; channel j = 0 .. 8 (cube r g b, second cube r g b, marker r g b):
+ *            u = (w[1 + j] >> 8) / 2^24, value = min(fma(u, hi - lo, lo), hi) in float32.  Keyed by the GLOBAL env id: every sharding of a job draws the same looks.
+ *   episode  count of an env: 0 after lcr_create, + 1 on every reset of the env -- lcr_reset (masked or not) and the auto-reset of lcr_step.  With a sampler a reset
+ *            redraws the look from the new count (a small kernel behind the step / reset kernel, before the frames are drawn); the look the env had is kept as its
+ *            TERMINAL look, with which lcr_render_terminal / lcr_render_terminal_planes draw the episode that ended.
+ *   who draws with which look: the batched frames (and planes) the env's current look; lcr_render / lcr_render_planes of env e that env's look -- cameras 0 and 1 are the
+ *            variant's, camera 2 is camera_vizu unmoved with the variant's colours and light; lcr_render_state / lcr_render_state_planes keep the default look. */
+#define LCR_LOOK_MAX_VARIANTS 64
+typedef struct lcr_look_variant {      /* index 0 = camera_front, 1 = camera_top */
+    float cam_dpos[2][3];    /* metres, world frame, added to the scene camera's position; |.| <= 0.2 per component, the camera stays >= 0.05 m above the floor */
+    float cam_drot[2][3];    /* rotation vector, world frame: the camera axes X, Y, Z are rotated by |r| rad about r / |r|; 0 = none; |r| <= 0.5 */
+    float fovy_deg[2];       /* 45; in [20, 90] */
+    float floor_rgb[2][3];   /* checker cells: odd (0.2, 0.3, 0.4), even (0.1, 0.2, 0.3) */
+    float sky_rgb[3], sky_slope[3];   /* colour = sky_rgb + a * sky_slope, a = clamp(2 * normalised d.z, 0, 1); both (0.15, 0.25, 0.35) */
+    float ambient, diffuse;  /* 0.3, 0.6: floor, base, arm, cubes, marker; each in [0, 1.5] */
+    float arm_rgb[3], finger_rgb[3];  /* base_link .. link_4: 0.8 grey; link_5, link_6: 0.75 grey */
+} lcr_look_variant;
+typedef struct lcr_look_sampler {      /* redraw an env's look whenever it is reset */
+    uint64_t seed;
+    float cube_lo[3], cube_hi[3], cube2_lo[3], cube2_hi[3], marker_lo[3], marker_hi[3];   /* per channel uniform in [lo, hi] within [0, 1]; lo == hi pins it */
+} lcr_look_sampler;
+/* Every colour lies in [0, 1] and every number is finite. */
+int lcr_look_variant_default(lcr_look_variant *v);   /* the values in the comments above */
+/* Switch the look on.  The arguments are checked before the handle is looked at (LCR_ERR_INVALID with the field's name in the message); then a NULL handle, a handle without
+ * image observations, a moved camera less than 5 cm above the floor and a handle whose planes are already enabled (enable the look first, the planes second) are refused.
+ * Builds the 2 n_variants cameras in fp64 (an all-zero offset gives the very floats of the scene cameras), ray-casts the n_variants cached background pairs, gives every env
+ * variant 0 and its task's colours -- with a sampler the draw of episode 0 -- and redraws the frames.  Fixed for the life of the handle: a second call with the same
+ * arguments does nothing, one with other arguments is refused. */
+int lcr_enable_look(lcr_sim *sim, int n_variants, const lcr_look_variant *variants_host, const lcr_look_sampler *sampler_or_null);
+/* The checkpoint of the look, beside lcr_get_state / lcr_set_state.  lcr_set_look: mask_host N bytes (NULL = all), variant_host / rgb_host may each be NULL (left as it is);
+ * the values of the masked envs are checked (variant in [0, n_variants), colours in [0, 1]); redraws the frames as a masked lcr_reset does.  Synchronous. */
+int lcr_set_look(lcr_sim *sim, const uint8_t *mask_host, const int32_t *variant_host /*[N]*/, const float *rgb_host /*[9][N]: cube, cube2, marker*/);
+int lcr_get_look(lcr_sim *sim, int32_t *variant /*[N]*/, float *rgb /*[9][N]*/, uint32_t *episode /*[N]*/);   /* any may be NULL */
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */

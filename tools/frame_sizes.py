@@ -1,11 +1,14 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task] [--planes]
+    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
   (ii) step + frames, closed loop (a sync after every step, what a policy that reads the frames sees) and open loop (steps enqueued back to back): env-steps/s.
 --planes: (i) once more with the depth plane, the segmentation plane and both switched on (VecSim(image_planes=...)): the frame kernel then writes 3 + 4 / 3 + 1 / 3 + 4 + 1 bytes
 per pixel, so a store-bound kernel would take 7/3, 4/3 and 8/3 of the plain time; the measured ratio is printed beside that.
+--look K[,K...] (e.g. --look 1,8,64): ONLY (i), at 240x320 and 84x84, for the build without a look and with a look of K variants (VecSim(look_variants=...): K different
+camera pairs, floors, skies and lights, variants and colours spread over the envs by the sampler): the same bytes are written, what changes is where the untouched bands are copied
+from -- K cached background pairs instead of one.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -17,7 +20,8 @@ import numpy as np  # noqa: E402
 from gym_lowcostrobot_amd import VecSim  # noqa: E402
 
 PLANES = "--planes" in sys.argv
-args = [a for a in sys.argv[1:] if a != "--planes"]
+LOOK = [int(k) for k in sys.argv[sys.argv.index("--look") + 1].split(",")] if "--look" in sys.argv else []
+args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--planes", "--look") and sys.argv[i - 1] != "--look"]
 n = int(args[0]) if len(args) > 0 else 32768
 task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
@@ -44,6 +48,39 @@ def frame_kernel_ms(sim):
         w.append(sim.timer_end() / 10)
     return float(np.median(w)), min(w), max(w)
 
+
+def look_variants(K):
+    """K variants, the first the default, the others with cameras, field of view, colours and light of their own (seeded)"""
+    rng = np.random.default_rng(1)
+    out = [{}]
+    for _ in range(K - 1):
+        out.append({"cam_dpos": rng.uniform(-0.08, 0.08, (2, 3)), "cam_drot": rng.uniform(-0.1, 0.1, (2, 3)), "fovy_deg": rng.uniform(35.0, 60.0, 2),
+                    "floor_rgb": rng.uniform(0.05, 0.6, (2, 3)), "sky_rgb": rng.uniform(0.05, 0.5, 3), "sky_slope": rng.uniform(0.0, 0.4, 3),
+                    "ambient": rng.uniform(0.2, 0.5), "diffuse": rng.uniform(0.4, 0.9), "arm_rgb": rng.uniform(0.3, 0.9, 3), "finger_rgb": rng.uniform(0.3, 0.9, 3)})
+    return out
+
+
+if LOOK:
+    print(f"frame kernel with a look ({n} envs): ms per launch (median of {WINDOWS} windows of ten), ratio to the build without a look, TB/s written, MB of cached backgrounds")
+    for H, W in [(240, 320), (84, 84)]:
+        base_ms = None
+        for K in [0] + LOOK:
+            kw = {} if K == 0 else {"look_variants": look_variants(K), "look_sampler": {"seed": 3, "cube": ([0.1] * 3, [0.9] * 3), "cube2": ([0.1] * 3, [0.9] * 3)}}
+            sim = VecSim(task, n, observation_mode="both", image_size=(H, W), **kw)
+            act = sim.alloc_actions()
+            for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+                sim.fill_random_actions(act, 1, t % 8)
+                sim.step_device(act.ptr)
+            if K:
+                assert len(set(sim.look()["variant"].tolist())) == K
+            ms, wmin, wmax = frame_kernel_ms(sim)
+            base_ms = ms if K == 0 else base_ms
+            nbytes = 2 * H * W * 3 * n
+            print(f"{H:4d}x{W:<4d} {'no look' if K == 0 else 'K = %2d' % K:>8s} {ms:8.3f} (min {wmin:.3f} max {wmax:.3f})  x{ms / base_ms:.3f}  {nbytes / ms / 1e9:6.2f} TB/s  "
+                  f"{max(K, 1) * 2 * H * W * 3 / 1e6:7.2f} MB", flush=True)
+            sim.free(act)
+            sim.close()
+    sys.exit(0)
 
 plane_rows = []
 for H, W in SIZES:
