@@ -30,6 +30,7 @@ PLANE_DEPTH, PLANE_SEGMENTATION = 1, 2   # LCR_PLANE_*: bits of lcr_enable_image
 IMAGE_PLANES = {"depth": PLANE_DEPTH, "segmentation": PLANE_SEGMENTATION}
 
 LOOK_MAX_VARIANTS = 64   # LCR_LOOK_MAX_VARIANTS
+WRIST_GUARD, WRIST_GUARD_BYTE = 4096, 0xA5   # LCR_WRIST_GUARD, LCR_WRIST_GUARD_BYTE: the guard regions around the wrist camera's buffers
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -43,6 +44,7 @@ SYMBOLS = [
     "lcr_calibrate_copy", "lcr_render", "lcr_render_state", "lcr_render_terminal", "lcr_step_kernel_family",
     "lcr_enable_image_planes", "lcr_get_image_planes", "lcr_render_planes", "lcr_render_state_planes", "lcr_render_terminal_planes",
     "lcr_look_variant_default", "lcr_enable_look", "lcr_set_look", "lcr_get_look",
+    "lcr_wrist_camera_default", "lcr_wrist_camera_check", "lcr_enable_wrist_camera", "lcr_get_wrist_camera", "lcr_render_terminal_wrist",
 ]
 
 
@@ -187,6 +189,62 @@ class LookSampler(ctypes.Structure):
         return out
 
 
+class WristCamera(ctypes.Structure):
+    """lcr_wrist_camera: the mount of the optional third observation camera (include/lcr.h)"""
+    _fields_ = [
+        ("link", ctypes.c_int32),          # 0 = world frame, 1 .. 6 = body frame of link_1 .. link_6
+        ("pos", ctypes.c_float * 3),       # metres in that frame
+        ("xyaxes", ctypes.c_float * 6),    # MuJoCo's camera xyaxes in that frame: X then Y
+        ("fovy_deg", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {"link": int(self.link), "pos": tuple(float(x) for x in self.pos), "xyaxes": tuple(float(x) for x in self.xyaxes), "fovy_deg": float(self.fovy_deg)}
+
+    @classmethod
+    def from_any(cls, v):
+        """a WristCamera, True (the default mount), or a dict of some of link / pos / xyaxes / fovy_deg over the default mount"""
+        if isinstance(v, cls):
+            return v
+        out = cls()
+        check(load().lcr_wrist_camera_default(ctypes.byref(out)))
+        if v is True:
+            return out
+        if not isinstance(v, dict):
+            raise ValueError(f"wrist_camera must be None, True or a dict of link / pos / xyaxes / fovy_deg, got {v!r}")
+        v = dict(v)
+        try:
+            if "link" in v:
+                out.link = int(v.pop("link"))
+            if "fovy_deg" in v:
+                out.fovy_deg = float(v.pop("fovy_deg"))
+            for name, cnt in (("pos", 3), ("xyaxes", 6)):
+                if name in v:
+                    vals = [float(x) for x in v.pop(name)]
+                    if len(vals) != cnt:
+                        raise ValueError(f"wrist_camera: {name} takes {cnt} numbers, got {len(vals)}")
+                    for i, x in enumerate(vals):
+                        getattr(out, name)[i] = x
+        except TypeError:
+            raise ValueError("wrist_camera: link is an integer, fovy_deg a number, pos three and xyaxes six numbers") from None
+        if v:
+            raise ValueError(f"unknown wrist camera fields {sorted(v)}")
+        return out
+
+
+class LcrWristView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("camera", WristCamera),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("depth_far", ctypes.c_float),
+        ("image_wrist", ctypes.c_void_p),  # [N][H][W][3] uint8
+        ("depth_wrist", ctypes.c_void_p),  # [N][H][W] float32 or NULL
+        ("seg_wrist", ctypes.c_void_p),    # [N][H][W] uint8 or NULL
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -303,6 +361,11 @@ def load():
     L.lcr_enable_look.argtypes = [vp, ctypes.c_int, ctypes.POINTER(LookVariant), ctypes.POINTER(LookSampler)]
     L.lcr_set_look.argtypes = [vp, vp, vp, vp]
     L.lcr_get_look.argtypes = [vp, vp, vp, vp]
+    L.lcr_wrist_camera_default.argtypes = [ctypes.POINTER(WristCamera)]
+    L.lcr_wrist_camera_check.argtypes = [ctypes.POINTER(WristCamera)]
+    L.lcr_enable_wrist_camera.argtypes = [vp, ctypes.POINTER(WristCamera)]
+    L.lcr_get_wrist_camera.argtypes = [vp, ctypes.POINTER(LcrWristView)]
+    L.lcr_render_terminal_wrist.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

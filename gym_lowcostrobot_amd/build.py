@@ -39,6 +39,8 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          ("lcr_render.hip", "lcr_render_planes.o", ["-DLCR_RENDER_PART=3"]),
          # the kernels that draw with a look (lcr_enable_look): frame kernels with and without planes, the backgrounds of the variants, the single-frame and redraw kernels
          ("lcr_render.hip", "lcr_render_look.o", ["-DLCR_RENDER_PART=4"]),
+         # the kernels of the wrist camera (lcr_enable_wrist_camera): the batched frame kernel with and without planes and looks, and its single-frame kernel
+         ("lcr_render.hip", "lcr_render_wrist.o", ["-DLCR_RENDER_PART=5"]),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),

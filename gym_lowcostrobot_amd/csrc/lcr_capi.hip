@@ -138,19 +138,48 @@ struct lcr_sim {
     lcr_look_variant *look_variants;   // host copies of the arguments of lcr_enable_look
     lcr_look_sampler look_sampler;
     bool look_has_sampler;
+    // the wrist camera (lcr_enable_wrist_camera): its frames are one allocation, its planes live in planes_mem; fixed for the life of the handle
+    bool wrist_on;
+    lcr_wrist_camera wrist_cam;  // the arguments of lcr_enable_wrist_camera
+    LcrWrist wrist;              // the arguments of the kernels that draw it
+    void *wrist_mem;
 };
 
 // whatever draws the handle's colour frames draws its enabled planes in the same launch
 // (`look`: the looks to draw P's envs with when they are not the current ones -- a snapshot)
-static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look = nullptr) {
-    if (s->look_K) {
-        LcrLook LK = s->look;
-        if (look) { LK.variant = look; LK.rgb = (const float *)(look + P.n); }
-        return lcr_launch_render_obs_look(P, LK, s->planes ? &s->pl : nullptr, stream);
-    }
-    if (s->planes) return lcr_launch_render_obs_planes(P, s->cam_front, s->cam_top, s->pl, stream);
-    return lcr_launch_render_obs(P, s->cam_front, s->cam_top, stream);
+// the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
+static LcrLook look_args(const lcr_sim *s, const LcrDev &P, const int *look) {
+    LcrLook LK = s->look;
+    if (look) { LK.variant = look; LK.rgb = (const float *)(look + P.n); }
+    return LK;
 }
+
+// the wrist frames (and planes) of P's envs, behind the two colour frames on the same stream
+static int launch_wrist_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look = nullptr) {
+    if (!s->look_K) return lcr_launch_render_wrist(P, s->wrist, nullptr, stream);
+    const LcrLook LK = look_args(s, P, look);
+    return lcr_launch_render_wrist(P, s->wrist, &LK, stream);
+}
+
+static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look = nullptr) {
+    int rc;
+    if (s->look_K) rc = lcr_launch_render_obs_look(P, look_args(s, P, look), s->planes ? &s->pl : nullptr, stream);
+    else if (s->planes) rc = lcr_launch_render_obs_planes(P, s->cam_front, s->cam_top, s->pl, stream);
+    else rc = lcr_launch_render_obs(P, s->cam_front, s->cam_top, stream);
+    if (!rc && s->wrist_on) rc = launch_wrist_frames(s, P, stream, look);
+    return rc;
+}
+
+// the wrist camera's mount with the ray scale of a frame `height` rows high (s = 2 tan(fovy / 2) / height in fp64, then rounded)
+static LcrWristMount wrist_mount_at(const lcr_sim *s, int height) {
+    LcrWristMount M = s->wrist.mount;
+    M.s = (float)(2.0 * std::tan(0.5 * (double)s->wrist_cam.fovy_deg * M_PI / 180.0) / height);
+    return M;
+}
+// the cameras a single-frame call accepts: 3 (the wrist camera) on a handle that has one
+#define CAMCHK(s, camera)                                                                                                   \
+    if ((camera) < 0 || (camera) > ((s)->wrist_on ? 3 : 2))                                                                 \
+        return fail(LCR_ERR_INVALID, (s)->wrist_on ? "camera must be 0 (front), 1 (top), 2 (vizu) or 3 (wrist)" : "camera must be 0 (front), 1 (top) or 2 (vizu)")
 
 static int join_render(lcr_sim *s) {
     if (s->rpending) {
@@ -566,6 +595,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->term_stage) (void)hipFree(s->term_stage);
     if (s->planes_mem) (void)hipFree(s->planes_mem);
     if (s->look_mem) (void)hipFree(s->look_mem);
+    if (s->wrist_mem) (void)hipFree(s->wrist_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -845,7 +875,7 @@ int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *
     SIMCHK(s);
     if (!rgb_host) return fail(LCR_ERR_INVALID, "rgb_host is NULL");
     if (env < 0 || env >= s->dev.n) return fail(LCR_ERR_INVALID, "env %d out of range", env);
-    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    CAMCHK(s, camera);
     if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
     LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
     cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
@@ -858,7 +888,9 @@ int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *
         s->render_bytes = bytes;
     }
     int rc;
-    if (s->look_K) {   // env's own look: cameras 0 and 1 are its variant's, camera_vizu stays where it is; the variant's colours and light, the env's colours
+    if (camera == 3)   // the wrist camera of env's pose, with env's look where the handle has one
+        rc = lcr_launch_render_single_wrist(s->dev, wrist_mount_at(s, height), env, width, height, 0.f, s->render_dev, nullptr, nullptr, s->look_K ? &s->look : nullptr, env, s->dev.n, s->stream);
+    else if (s->look_K) {   // env's own look: cameras 0 and 1 are its variant's, camera_vizu stays where it is; the variant's colours and light, the env's colours
         if (camera < 2) {
             int v = 0;
             if (int lr = look_variant_of(s, env, &v)) return lr;
@@ -875,7 +907,7 @@ int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *
 int lcr_render_state(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, uint8_t *rgb_host) {
     SIMCHK(s);
     if (!rgb_host || !qpos_host) return fail(LCR_ERR_INVALID, "NULL argument");
-    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    CAMCHK(s, camera);
     if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
     LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
     cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
@@ -897,10 +929,41 @@ int lcr_render_state(lcr_sim *s, int camera, int width, int height, const double
     P1.n = 1;
     P1.qpos = stage;
     P1.target = stage + s->nq;
-    int rc = lcr_launch_render_single(P1, cam, 0, width, height, s->render_dev, s->stream);
+    int rc = camera == 3 ? lcr_launch_render_single_wrist(P1, wrist_mount_at(s, height), 0, width, height, 0.f, s->render_dev, nullptr, nullptr, nullptr, -1, 1, s->stream)
+                         : lcr_launch_render_single(P1, cam, 0, width, height, s->render_dev, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(rgb_host, s->render_dev, bytes, hipMemcpyDeviceToHost));
+    return LCR_OK;
+}
+
+// ---- the staging of the three terminal-frame calls (lcr_render_terminal, lcr_render_terminal_planes, lcr_render_terminal_wrist) ----
+// grows the staging buffer to `need` bytes
+static int term_stage_reserve(lcr_sim *s, size_t need) {
+    if (need <= s->term_stage_bytes) return LCR_OK;
+    if (s->term_stage) (void)hipFree(s->term_stage);
+    s->term_stage = nullptr; s->term_stage_bytes = 0;
+    hipError_t e = hipMalloc(&s->term_stage, need);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+    s->term_stage_bytes = need;
+    return LCR_OK;
+}
+// one pass: `c` env ids to the device, their terminal poses gathered behind them and -- with a look -- their terminal looks.  P1: the c-env view of the handle over the
+// gathered poses (the caller points its frame buffers into the staging), LK: the looks to draw it with
+static int term_stage_gather(lcr_sim *s, const int32_t *ids_host, int c, char *base, size_t o_ids, size_t o_q, size_t o_t, size_t o_lk, LcrDev &P1, LcrLook &LK) {
+    HIPCHK(hipMemcpyAsync(base + o_ids, ids_host, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
+    int rc = lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream);
+    if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+    P1 = s->dev;
+    P1.n = c;
+    P1.qpos = (float *)(base + o_q);
+    P1.target = (float *)(base + o_t);
+    LK = LcrLook{};
+    if (s->look_K) {
+        rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
+        LK = look_args(s, P1, (const int *)(base + o_lk));
+    }
     return LCR_OK;
 }
 
@@ -918,32 +981,18 @@ int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_ids = 0, o_q = al(sizeof(int) * cap), o_t = o_q + al(sizeof(float) * s->nq * cap), o_f = o_t + al(sizeof(float) * 3 * cap),
                  o_tp = o_f + al(img * cap), o_lk = o_tp + al(img * cap), need = o_lk + (s->look_K ? al(sizeof(int) * 10 * cap) : 0);   // (o_lk: the terminal looks of the listed envs)
-    if (need > s->term_stage_bytes) {
-        if (s->term_stage) (void)hipFree(s->term_stage);
-        s->term_stage = nullptr; s->term_stage_bytes = 0;
-        hipError_t e = hipMalloc((void **)&s->term_stage, need);
-        if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        s->term_stage_bytes = need;
-    }
+    if (int rc = term_stage_reserve(s, need)) return rc;
     char *base = (char *)s->term_stage;
     for (int done = 0; done < count; done += cap) {
         const int c = count - done < cap ? count - done : cap;
-        HIPCHK(hipMemcpyAsync(base + o_ids, env_ids_host + done, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
-        int rc = lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-        LcrDev P1 = s->dev;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
-        P1.n = c;
-        P1.qpos = (float *)(base + o_q);
-        P1.target = (float *)(base + o_t);
+        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
+        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
+        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
+        if (rc) return rc;
         P1.img_front = (unsigned char *)(base + o_f);
         P1.img_top = (unsigned char *)(base + o_tp);
-        if (s->look_K) {   // the episode that ended is drawn as it looked
-            rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
-            if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-            LcrLook LK = s->look;
-            LK.variant = (const int *)(base + o_lk); LK.rgb = (const float *)(base + o_lk) + c;
-            rc = lcr_launch_render_obs_look(P1, LK, nullptr, s->stream);
-        } else rc = lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream);
+        if (s->look_K) rc = lcr_launch_render_obs_look(P1, LK, nullptr, s->stream);
+        else rc = lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         HIPCHK(hipMemcpyAsync(front_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipMemcpyAsync(top_host + (size_t)done * img, base + o_tp, img * c, hipMemcpyDeviceToHost, s->stream));
@@ -990,6 +1039,10 @@ int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
     const size_t o_d1 = off; if (dep) off += al(N * px * sizeof(float));
     const size_t o_s0 = off; if (seg) off += al(N * px);
     const size_t o_s1 = off; if (seg) off += al(N * px);
+    // the planes cover the wrist camera; LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE before, between and behind them (include/lcr.h)
+    const size_t o_g2 = off; if (s->wrist_on) off += LCR_WRIST_GUARD;
+    const size_t o_d2 = off; if (dep && s->wrist_on) off += al(N * px * sizeof(float)) + LCR_WRIST_GUARD;
+    const size_t o_s2 = off; if (seg && s->wrist_on) off += al(N * px) + LCR_WRIST_GUARD;
     void *mem = nullptr;
     hipError_t e = hipMalloc(&mem, off);
     if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the image planes failed: %s", off, hipGetErrorString(e));
@@ -1011,8 +1064,17 @@ int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
         rc = lcr_launch_render_bg_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
         if (!rc) rc = lcr_launch_render_obs_planes(s->dev, s->cam_front, s->cam_top, PL, s->stream);
     }
+    LcrWrist WR = s->wrist;
+    if (s->wrist_on) {
+        if (!rc) rc = (int)hipMemsetAsync(base + o_g2, LCR_WRIST_GUARD_BYTE, off - o_g2, s->stream);
+        WR.depth = dep ? (float *)(base + o_d2) : nullptr;
+        WR.seg = seg ? (unsigned char *)(base + o_s2) : nullptr;
+        WR.far = depth_far;
+        if (!rc) rc = lcr_launch_render_wrist(s->dev, WR, s->look_K ? &s->look : nullptr, s->stream);
+    }
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
     if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "drawing the image planes failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->wrist = WR;
     s->pl = PL;
     s->planes_mem = mem;
     s->planes = planes;
@@ -1047,7 +1109,10 @@ static int render_planes_of(lcr_sim *s, const LcrDev &P, int env, int camera, in
     }
     const size_t px = (size_t)width * height;
     const float far = s->planes ? s->pl.far : 10.f;
-    int rc = lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_host ? (float *)s->render_dev : nullptr, seg_host ? s->render_dev + o_seg : nullptr, s->stream);
+    float *depth_dev = depth_host ? (float *)s->render_dev : nullptr;
+    unsigned char *seg_dev = seg_host ? s->render_dev + o_seg : nullptr;
+    int rc = camera == 3 ? lcr_launch_render_single_wrist(P, wrist_mount_at(s, height), env, width, height, far, nullptr, depth_dev, seg_dev, nullptr, -1, 1, s->stream)
+                         : lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_dev, seg_dev, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (depth_host) HIPCHK(hipMemcpy(depth_host, s->render_dev, px * sizeof(float), hipMemcpyDeviceToHost));
@@ -1059,7 +1124,7 @@ int lcr_render_planes(lcr_sim *s, int env, int camera, int width, int height, fl
     SIMCHK(s);
     if (!depth_host && !seg_host) return fail(LCR_ERR_INVALID, "depth_host and seg_host are both NULL");
     if (env < 0 || env >= s->dev.n) return fail(LCR_ERR_INVALID, "env %d out of range", env);
-    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    CAMCHK(s, camera);
     if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
     const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255;
     if (int rc = ensure_render_scratch(s, o_seg + px)) return rc;
@@ -1069,7 +1134,7 @@ int lcr_render_planes(lcr_sim *s, int env, int camera, int width, int height, fl
 int lcr_render_state_planes(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, float *depth_host, uint8_t *seg_host) {
     SIMCHK(s);
     if (!qpos_host || (!depth_host && !seg_host)) return fail(LCR_ERR_INVALID, "NULL argument");
-    if (camera < 0 || camera > 2) return fail(LCR_ERR_INVALID, "camera must be 0 (front), 1 (top) or 2 (vizu)");
+    CAMCHK(s, camera);
     if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
     const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255, o_pose = (o_seg + px + 255) & ~(size_t)255;
     if (int rc = ensure_render_scratch(s, o_pose + 256)) return rc;
@@ -1112,23 +1177,14 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
     const size_t o_s0 = off; if (seg) off += al(px * cap);
     const size_t o_s1 = off; if (seg) off += al(px * cap);
     const size_t o_lk = off; if (s->look_K) off += al(sizeof(int) * 10 * cap);   // the terminal looks of the listed envs
-    if (off > s->term_stage_bytes) {
-        if (s->term_stage) (void)hipFree(s->term_stage);
-        s->term_stage = nullptr; s->term_stage_bytes = 0;
-        hipError_t e = hipMalloc((void **)&s->term_stage, off);
-        if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
-        s->term_stage_bytes = off;
-    }
+    if (int rc = term_stage_reserve(s, off)) return rc;
     char *base = (char *)s->term_stage;
     for (int done = 0; done < count; done += cap) {
         const int c = count - done < cap ? count - done : cap;
-        HIPCHK(hipMemcpyAsync(base + o_ids, env_ids_host + done, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
-        int rc = lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-        LcrDev P1 = s->dev;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
-        P1.n = c;
-        P1.qpos = (float *)(base + o_q);
-        P1.target = (float *)(base + o_t);
+        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
+        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
+        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
+        if (rc) return rc;
         P1.img_front = (unsigned char *)(base + o_f);
         P1.img_top = (unsigned char *)(base + o_tp);
         LcrPlanes PL1 = s->pl;
@@ -1136,13 +1192,8 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
         PL1.depth_top = dep ? (float *)(base + o_d1) : nullptr;
         PL1.seg_front = seg ? (unsigned char *)(base + o_s0) : nullptr;
         PL1.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
-        if (s->look_K) {
-            rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
-            if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-            LcrLook LK = s->look;
-            LK.variant = (const int *)(base + o_lk); LK.rgb = (const float *)(base + o_lk) + c;
-            rc = lcr_launch_render_obs_look(P1, LK, &PL1, s->stream);
-        } else rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
+        if (s->look_K) rc = lcr_launch_render_obs_look(P1, LK, &PL1, s->stream);
+        else rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
         if (dep) {
             HIPCHK(hipMemcpyAsync(depth_front + (size_t)done * px, base + o_d0, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
@@ -1302,6 +1353,11 @@ int lcr_enable_look(lcr_sim *s, int n_variants, const lcr_look_variant *variants
     s->look_has_sampler = sampler != nullptr;
     if (sampler) s->look_sampler = *sampler;
     s->look_K = n_variants;
+    if (s->wrist_on) {   // the wrist frames take the look as well
+        rc = launch_wrist_frames(s, s->dev, s->stream);
+        if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "drawing the wrist frames with the look failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     return LCR_OK;
 }
 
@@ -1340,6 +1396,144 @@ int lcr_get_look(lcr_sim *s, int32_t *variant, float *rgb, uint32_t *episode) {
     if (variant) HIPCHK(hipMemcpy(variant, s->look_cur, sizeof(int) * N, hipMemcpyDeviceToHost));
     if (rgb) HIPCHK(hipMemcpy(rgb, s->look_cur + N, sizeof(float) * 9 * N, hipMemcpyDeviceToHost));
     if (episode) HIPCHK(hipMemcpy(episode, s->look_episode, sizeof(unsigned) * N, hipMemcpyDeviceToHost));
+    return LCR_OK;
+}
+
+// ---- the wrist camera ----
+
+int lcr_wrist_camera_default(lcr_wrist_camera *cam) {
+    if (!cam) return fail(LCR_ERR_INVALID, "cam is NULL");
+    memset(cam, 0, sizeof *cam);
+    cam->link = 5;
+    cam->pos[0] = 0.03f; cam->pos[1] = 0.0033f; cam->pos[2] = 0.045f;
+    const float xy[6] = {0.f, 1.f, 0.f, -0.4226f, 0.f, 0.9063f};   // 25 degrees down along the gripper's -x
+    memcpy(cam->xyaxes, xy, sizeof xy);
+    cam->fovy_deg = 60.f;
+    return LCR_OK;
+}
+
+// checks `cam` (include/lcr.h) and finishes its axes in fp64 as cam_finish does for the scene cameras; `height`: rows of the frames it draws
+static int wrist_mount(const lcr_wrist_camera *cam, int height, LcrWristMount *out) {
+    if (!cam) return fail(LCR_ERR_INVALID, "cam is NULL");
+    if (cam->link < 0 || cam->link > 6) return fail(LCR_ERR_INVALID, "link must be 0 (world frame) or 1 .. 6 (link_1 .. link_6), got %d", cam->link);
+    const float reach = cam->link == 0 ? 2.f : 0.5f;
+    if (!in_range(cam->pos, 3, -reach, reach)) return fail(LCR_ERR_INVALID, "pos must be finite and within +-%g m per component in the frame of link %d", (double)reach, cam->link);
+    if (cam->link == 0 && cam->pos[2] < 0.05f) return fail(LCR_ERR_INVALID, "pos leaves a world-frame camera %.3f m above the floor, less than 0.05 m", (double)cam->pos[2]);
+    for (int i = 0; i < 6; i++)
+        if (!finite_f(cam->xyaxes[i])) return fail(LCR_ERR_INVALID, "xyaxes must be finite");
+    if (!in_range(&cam->fovy_deg, 1, 20.f, 120.f)) return fail(LCR_ERR_INVALID, "fovy_deg must be finite and in [20, 120]");
+    double X[3], Y[3];
+    for (int i = 0; i < 3; i++) { X[i] = (double)cam->xyaxes[i]; Y[i] = (double)cam->xyaxes[3 + i]; }
+    const double nx = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
+    if (!(nx > 0.0)) return fail(LCR_ERR_INVALID, "xyaxes: X is zero");
+    for (int i = 0; i < 3; i++) X[i] /= nx;
+    const double d = X[0] * Y[0] + X[1] * Y[1] + X[2] * Y[2];
+    for (int i = 0; i < 3; i++) Y[i] -= d * X[i];
+    const double ny = std::sqrt(Y[0] * Y[0] + Y[1] * Y[1] + Y[2] * Y[2]);
+    if (ny < 1e-6) return fail(LCR_ERR_INVALID, "xyaxes: Y is parallel to X (norm %.3g after its projection on X is removed)", ny);
+    for (int i = 0; i < 3; i++) Y[i] /= ny;
+    const double Z[3] = {X[1] * Y[2] - X[2] * Y[1], X[2] * Y[0] - X[0] * Y[2], X[0] * Y[1] - X[1] * Y[0]};
+    LcrWristMount &M = *out;
+    M.link = cam->link;
+    M.px = cam->pos[0]; M.py = cam->pos[1]; M.pz = cam->pos[2];
+    M.xx = (float)X[0]; M.xy = (float)X[1]; M.xz = (float)X[2];
+    M.yx = (float)Y[0]; M.yy = (float)Y[1]; M.yz = (float)Y[2];
+    M.zx = (float)Z[0]; M.zy = (float)Z[1]; M.zz = (float)Z[2];
+    M.s = (float)(2.0 * std::tan(0.5 * (double)cam->fovy_deg * M_PI / 180.0) / height);
+    return LCR_OK;
+}
+
+int lcr_wrist_camera_check(const lcr_wrist_camera *cam) {
+    LcrWristMount M;
+    return wrist_mount(cam, LCR_IMG_H, &M);
+}
+
+int lcr_enable_wrist_camera(lcr_sim *s, const lcr_wrist_camera *cam) {
+    // the argument first, the handle afterwards (what can be refused without a device is)
+    LcrWristMount M;
+    if (int rc = wrist_mount(cam, s ? s->dev.img_h : LCR_IMG_H, &M)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to add a wrist camera to");
+    if (s->wrist_on) {
+        if (memcmp(&s->wrist_cam, cam, sizeof *cam) == 0) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "a wrist camera on link %d is enabled already and fixed for the life of the handle", s->wrist_cam.link);
+    }
+    if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the wrist camera first and the planes second (they then cover it)");
+    // the frames between two guard regions (include/lcr.h: LCR_WRIST_GUARD)
+    const size_t bytes = (((size_t)s->dev.n * s->dev.img_h * s->dev.img_w * 3 + 255) & ~(size_t)255) + 2 * LCR_WRIST_GUARD;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the wrist frames failed: %s", bytes, hipGetErrorString(e));
+    LcrWrist WR{};
+    WR.mount = M;
+    WR.img = (unsigned char *)mem + LCR_WRIST_GUARD;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, bytes, s->stream);
+    if (!rc) rc = lcr_launch_render_wrist(s->dev, WR, s->look_K ? &s->look : nullptr, s->stream);
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "drawing the wrist frames failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->wrist = WR;
+    s->wrist_mem = mem;
+    s->wrist_cam = *cam;
+    s->wrist_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_wrist_camera(lcr_sim *s, lcr_wrist_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the wrist frames are drawn on the second stream after a step: the handle's stream waits for them here)
+    memset(out, 0, sizeof *out);
+    if (!s->wrist_on) return LCR_OK;
+    out->enabled = 1;
+    out->camera = s->wrist_cam;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->depth_far = s->planes ? s->wrist.far : 0.f;
+    out->image_wrist = s->wrist.img;
+    out->depth_wrist = s->wrist.depth;
+    out->seg_wrist = s->wrist.seg;
+    return LCR_OK;
+}
+
+int lcr_render_terminal_wrist(lcr_sim *s, const int32_t *env_ids_host, int count, uint8_t *rgb_host, float *depth_host, uint8_t *seg_host) {
+    SIMCHK(s);
+    if (!s->wrist_on) return fail(LCR_ERR_INVALID, "no wrist camera is enabled on this sim (lcr_enable_wrist_camera)");
+    if (count < 0 || (count > 0 && (!env_ids_host || !rgb_host))) return fail(LCR_ERR_INVALID, "NULL argument");
+    if ((depth_host && !s->wrist.depth) || (seg_host && !s->wrist.seg)) return fail(LCR_ERR_INVALID, "a plane that is not enabled was asked for (lcr_enable_image_planes)");
+    for (int i = 0; i < count; i++)
+        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, per_env = img + (depth_host ? px * sizeof(float) : 0) + (seg_host ? px : 0);
+    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass, as lcr_render_terminal
+    const size_t chunk = BUDGET / per_env;
+    const int cap = (size_t)count < chunk ? count : (int)chunk;
+    if (cap == 0) return LCR_OK;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = 0;
+    const size_t o_ids = off; off += al(sizeof(int) * cap);
+    const size_t o_q = off; off += al(sizeof(float) * s->nq * cap);
+    const size_t o_t = off; off += al(sizeof(float) * 3 * cap);
+    const size_t o_f = off; off += al(img * cap);
+    const size_t o_d = off; if (depth_host) off += al(px * sizeof(float) * cap);
+    const size_t o_s = off; if (seg_host) off += al(px * cap);
+    const size_t o_lk = off; if (s->look_K) off += al(sizeof(int) * 10 * cap);   // the terminal looks of the listed envs
+    if (int rc = term_stage_reserve(s, off)) return rc;
+    char *base = (char *)s->term_stage;
+    for (int done = 0; done < count; done += cap) {
+        const int c = count - done < cap ? count - done : cap;
+        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
+        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
+        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
+        if (rc) return rc;
+        LcrWrist W1 = s->wrist;
+        W1.img = (unsigned char *)(base + o_f);
+        W1.depth = depth_host ? (float *)(base + o_d) : nullptr;
+        W1.seg = seg_host ? (unsigned char *)(base + o_s) : nullptr;
+        rc = lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream);
+        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        HIPCHK(hipMemcpyAsync(rgb_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
+        if (depth_host) HIPCHK(hipMemcpyAsync(depth_host + (size_t)done * px, base + o_d, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
+        if (seg_host) HIPCHK(hipMemcpyAsync(seg_host + (size_t)done * px, base + o_s, px * c, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
     return LCR_OK;
 }
 

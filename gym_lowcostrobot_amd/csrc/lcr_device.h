@@ -116,6 +116,21 @@ struct LcrLookSampler {
     int on, K;
 };
 
+// the wrist camera (lcr_enable_wrist_camera): its mount in the frame of a link, axes finished on the host.  A kernel argument of its own, as LcrPlanes and LcrLook are
+struct LcrWristMount {
+    int link;                              // 0: world frame, 1 .. 6: body frame of link_1 .. link_6
+    float px, py, pz;                      // position in that frame
+    float xx, xy, xz, yx, yy, yz, zx, zy, zz;   // axes in that frame (the camera looks along -Z)
+    float s;                               // 2 tan(fovy / 2) / height of the frame it is asked to draw
+};
+struct LcrWrist {
+    LcrWristMount mount;
+    unsigned char *img;                    // [n][img_h][img_w][3]
+    float *depth;                          // [n][img_h][img_w] or null
+    unsigned char *seg;                    // [n][img_h][img_w] or null
+    float far;
+};
+
 // launchers implemented in lcr_kernels.hip / lcr_render.hip (plain C++ linkage, same shared object)
 int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
 // the Newton kernels of the faithful preset (lcr_kernels.hip, unit LCR_PART = 4)
@@ -149,3 +164,8 @@ int lcr_launch_render_single_look(const LcrDev &P, const LcrCam &cam, int env, i
 // mode 0: envs with flag[e] != 0 (null: all) count an episode and draw its look, `term` (or null) receives the look they had; 1: every env draws the look of episode 0
 int lcr_launch_look_redraw(int n, long long env_off, const unsigned char *flag, int mode, const LcrLookSampler &SM, int *cur, unsigned *episode, int *term, void *stream);
 int lcr_launch_look_gather(const int *ids_dev, int count, int n, const int *look, int *out, void *stream);
+// the wrist camera (lcr_render.hip, unit LCR_RENDER_PART = 5): the batched frames (+ the planes WR points at; LK: with the envs' looks, or null) / one env, one ray per
+// pixel into any of rgb_dev, depth_dev, seg_dev (look_env >= 0: with the look of env look_env of LK)
+int lcr_launch_render_wrist(const LcrDev &P, const LcrWrist &WR, const LcrLook *LK, void *stream);
+int lcr_launch_render_single_wrist(const LcrDev &P, const LcrWristMount &M, int env, int W, int H, float far, unsigned char *rgb_dev, float *depth_dev, unsigned char *seg_dev,
+                                   const LcrLook *LK, int look_env, int look_n, void *stream);

@@ -22,9 +22,9 @@
 
 using namespace lcrdev;
 
-// This file is compiled as four units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes, 3 = the
-// kernels that draw the depth / segmentation planes (include/lcr.h: lcr_enable_image_planes), 4 = the kernels that draw with a look (lcr_enable_look); undefined = everything in
-// one unit (the tools that compile this file on its own)
+// This file is compiled as five units (build.py): LCR_RENDER_PART 0 = the 320 x 240 frame kernel and the small kernels, 1 = the frame kernels for run-time sizes, 3 = the
+// kernels that draw the depth / segmentation planes (include/lcr.h: lcr_enable_image_planes), 4 = the kernels that draw with a look (lcr_enable_look), 5 = the kernels of the
+// wrist camera (lcr_enable_wrist_camera); undefined = everything in one unit (the tools that compile this file on its own)
 #ifndef LCR_RENDER_PART
 #define LCR_RENDER_PART 2
 #endif
@@ -32,6 +32,7 @@ using namespace lcrdev;
 #define LCR_RENDER_SIZED (LCR_RENDER_PART == 1 || LCR_RENDER_PART == 2)
 #define LCR_RENDER_PLANES (LCR_RENDER_PART == 3 || LCR_RENDER_PART == 2)
 #define LCR_RENDER_LOOK (LCR_RENDER_PART == 4 || LCR_RENDER_PART == 2)
+#define LCR_RENDER_WRIST (LCR_RENDER_PART == 5 || LCR_RENDER_PART == 2)
 
 namespace {
 
@@ -212,6 +213,14 @@ struct Shade {
     h.amb = 0.3f; h.dif = 0.6f;
     return h;
 }
+// ... and the values of a look variant (lcr_enable_look)
+[[maybe_unused]] DEV Shade look_shade(const LcrLookVar &V) {
+    Shade h;
+    h.floor_odd = mk(V.floor_rgb[0][0], V.floor_rgb[0][1], V.floor_rgb[0][2]); h.floor_even = mk(V.floor_rgb[1][0], V.floor_rgb[1][1], V.floor_rgb[1][2]);
+    h.sky = mk(V.sky_rgb[0], V.sky_rgb[1], V.sky_rgb[2]); h.sky_slope = mk(V.sky_slope[0], V.sky_slope[1], V.sky_slope[2]);
+    h.amb = V.ambient; h.dif = V.diffuse;
+    return h;
+}
 
 #if LCR_RENDER_SMALL || LCR_RENDER_LOOK   // (the per-pixel shading of the background and single-frame kernels)
 DEV f3 floor_or_sky(f3 ro, f3 d, float inv_len, float &tfloor, const Shade &h) {
@@ -309,7 +318,7 @@ __global__ __launch_bounds__(256) void lcr_render_bg_kernel(LcrDev P, LcrCam fro
 #endif
 
 // OR of a value over lanes 0 .. 15 (the primitives live in lanes 0 .. NPRIM-1): four row_shr DPP steps, the result is read from lane 15
-DEV unsigned or_row0(unsigned x) {
+[[maybe_unused]] DEV unsigned or_row0(unsigned x) {
     x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
     x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);   // row_shr:2
     x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);   // row_shr:4
@@ -670,14 +679,6 @@ __global__ __launch_bounds__(256) void lcr_gather_terminal_kernel(LcrDev P, cons
 
 #if LCR_RENDER_LOOK
 // ---- the look (include/lcr.h: lcr_enable_look) ----
-DEV Shade look_shade(const LcrLookVar &V) {
-    Shade h;
-    h.floor_odd = mk(V.floor_rgb[0][0], V.floor_rgb[0][1], V.floor_rgb[0][2]); h.floor_even = mk(V.floor_rgb[1][0], V.floor_rgb[1][1], V.floor_rgb[1][2]);
-    h.sky = mk(V.sky_rgb[0], V.sky_rgb[1], V.sky_rgb[2]); h.sky_slope = mk(V.sky_slope[0], V.sky_slope[1], V.sky_slope[2]);
-    h.amb = V.ambient; h.dif = V.diffuse;
-    return h;
-}
-
 // the cached backgrounds of the K variants, LK.bg [K][2][H][W][3]: lcr_render_bg_kernel with each variant's cameras, colours and light
 __global__ __launch_bounds__(256) void lcr_render_bg_look_kernel(LcrDev P, LcrLook LK, int K) {
     const int W = P.img_w, H = P.img_h, per = 2 * W * H;
@@ -792,6 +793,227 @@ __global__ __launch_bounds__(256) void lcr_look_gather_kernel(const int *ids, in
     if (i >= count) return;
     const int e = ids[i];
     for (int j = 0; j < 10; j++) out[(size_t)j * count + i] = look[(size_t)j * n + e];
+}
+#endif
+
+#if LCR_RENDER_WRIST
+// ---- the wrist camera (include/lcr.h: lcr_enable_wrist_camera) ----
+// A camera that rides on a link moves every step: it has no cached background.  Every 16 x 4 tile is shaded, floor or sky per pixel in registers, and only the boxes of the
+// tile's wave-uniform mask are tested.  A dedicated kernel: lcr_render_obs_kernel, its register budget and its bytes stay as they are.
+
+// the chain of link frames build_scene places the arm's boxes with (build_scene itself, shared with the two-camera kernels, stays as it is: exposing its frames moved their
+// register allocation)
+DEV void wrist_frames(const LcrDev &P, int env, ArmFrames &F) {
+    float q[6];
+    for (int j = 0; j < 6; j++) q[j] = P.qpos[(size_t)j * P.n + env];
+    arm_frames(q, F);
+}
+
+// world pose of the mounted camera, from the chain of link frames that places the arm's boxes: ro = p_link + R_link pos, axes = R_link axes (link 0: the numbers themselves).
+// The batched kernel and the single-frame kernel share it
+DEV void wrist_camera(const ArmFrames &F, const LcrWristMount &M, LcrCam &C) {
+    C.s = M.s;
+    if (M.link == 0) {
+        C.px = M.px; C.py = M.py; C.pz = M.pz;
+        C.xx = M.xx; C.xy = M.xy; C.xz = M.xz; C.yx = M.yx; C.yy = M.yy; C.yz = M.yz; C.zx = M.zx; C.zy = M.zy; C.zz = M.zz;
+        return;
+    }
+    f3 p, X, Y, Z;   // (literal indices: the chain stays in registers)
+    switch (M.link) {
+    case 1: p = F.p[0]; X = F.X[0]; Y = F.Y[0]; Z = F.Z[0]; break;
+    case 2: p = F.p[1]; X = F.X[1]; Y = F.Y[1]; Z = F.Z[1]; break;
+    case 3: p = F.p[2]; X = F.X[2]; Y = F.Y[2]; Z = F.Z[2]; break;
+    case 4: p = F.p[3]; X = F.X[3]; Y = F.Y[3]; Z = F.Z[3]; break;
+    case 5: p = F.p[4]; X = F.X[4]; Y = F.Y[4]; Z = F.Z[4]; break;
+    default: p = F.p[5]; X = F.X[5]; Y = F.Y[5]; Z = F.Z[5]; break;
+    }
+    const f3 ro = axpy(M.px, X, axpy(M.py, Y, axpy(M.pz, Z, p)));
+    const f3 cx = axpy(M.xx, X, axpy(M.xy, Y, M.xz * Z)), cy = axpy(M.yx, X, axpy(M.yy, Y, M.yz * Z)), cz = axpy(M.zx, X, axpy(M.zy, Y, M.zz * Z));
+    C.px = ro.x; C.py = ro.y; C.pz = ro.z;
+    C.xx = cx.x; C.xy = cx.y; C.xz = cx.z; C.yx = cy.x; C.yy = cy.y; C.yz = cy.z; C.zx = cz.x; C.zy = cz.y; C.zz = cz.z;
+}
+
+// one pixel of the wrist camera, the boxes of mask `m` (uniform; the marker is the last box): linear rgb, t of the nearest opaque surface along the un-normalised ray
+// (1e30: sky) and the segmentation byte.  The expressions of shade_pixel / trace_pixel, with the floor rule a camera on a link needs: the floor is seen only where the
+// normalised d.z < -1e-6 AND the camera is above it -- at or below the floor plane those rays take the sky formula and the floor limits no box (a negative floor parameter
+// would hide every box)
+DEV void wrist_pixel(const LcrCam &C, const float (*boxc)[16], const f3 *bcol, unsigned m, int marker, float sx, float sy, const Shade &h, f3 &out, float &tnear, unsigned &seg) {
+    const f3 ro = mk(C.px, C.py, C.pz);
+    const f3 d = mk(C.xx * sx + C.yx * sy - C.zx, C.xy * sx + C.yy * sy - C.zy, C.xz * sx + C.yz * sy - C.zz);
+    const float inv_len = rsq(dot(d, d));
+    const float rdz = d.z * inv_len;
+    const bool floor = rdz < -1e-6f && ro.z > 0.f;
+    float tbest = 1e30f;
+    if (floor) {   // checker floor, 0.1 m squares, normal +z
+        tbest = -ro.z * rcp(d.z);
+        const float fx = fmaf(tbest, d.x, ro.x), fy = fmaf(tbest, d.y, ro.y);
+        const int cell = ((int)floorf(fx * 10.f) + (int)floorf(fy * 10.f)) & 1;
+        const float lam = fminf(fmaf(-h.dif, rdz, h.amb), 1.f);
+        out = lam * (cell ? h.floor_odd : h.floor_even);
+    } else {
+        const float a = clampf(rdz * 2.f, 0.f, 1.f);
+        out = mk(h.sky.x + a * h.sky_slope.x, h.sky.y + a * h.sky_slope.y, h.sky.z + a * h.sky_slope.z);
+    }
+    int kbest = -1;
+    float talpha = 0.f, tlamd = 0.f;
+    for (unsigned mm = m; mm; mm &= mm - 1u) {
+        const int k = __builtin_ctz(mm);
+        float tmin, ld;
+        if (!box_hit(boxc[k], sx, sy, tbest, tmin, ld)) continue;
+        if (k == marker) { tlamd = ld; talpha = boxc[k][15]; }
+        else { tbest = tmin; kbest = k; out = fminf(fmaf(h.dif * inv_len, ld, h.amb), 1.f) * bcol[k]; }
+    }
+    if (talpha > 0.f) out = axpy(talpha * fmaf(h.dif * inv_len, tlamd, h.amb), bcol[marker < 0 ? 0 : marker], (1.f - talpha) * out);
+    tnear = tbest;
+    seg = (kbest >= 0 ? (unsigned)kbest + 2u : (floor ? 1u : 0u)) | (talpha > 0.f ? 0x80u : 0u);
+}
+
+// The batched wrist frames, [n][H][W][3] at the handle's frame size (run-time values), with the planes WR points at (PLANES) and the envs' looks (LOOK: the variant's floor,
+// sky, light and arm colours, the env's own colours; the variant's camera offsets belong to the two scene cameras).  The mapping of lcr_render_obs_kernel: a workgroup draws
+// EPW envs (1, 2, 4) with 4 / EPW waves each, a wave owns bands of 4 rows in turn; thread 0 of an env builds the scene and the camera, one thread per primitive its
+// culling record (build_prim: a primitive that crosses the plane 0.02 m in front of the camera -- the mounting link's own box usually does -- gets the full-frame record).
+// The band's bytes are staged in LDS (12 W B of colours, PLANES: 4 W B of segmentation behind them) and leave as non-temporal 16-B stores; the depth band goes straight
+// from registers, 64 B per tile row.
+template <bool PLANES, bool LOOK, int EPW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void lcr_render_wrist_kernel(LcrDev P, LcrWrist WR, LcrLook LK) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    static_assert(EPW == 1 || EPW == 2 || EPW == 4, "1, 2 or 4 waves per env");
+    static_assert(NPRIM <= 16, "one primitive per lane of a DPP row");
+    const int W = P.img_w, H = P.img_h;
+    const int NT = (W + 15) >> 4;   // 16-pixel tile columns, the last one partial when W % 16 != 0
+    const int VB = 3 * W / 4;       // 16-B vectors of a colour band
+    const int RB = 3 * W;           // bytes of a row
+    const int VS = W >> 2;          // 16-B vectors of a segmentation band
+    const int NB = H / 4;
+    __shared__ Scene S_[EPW];
+    __shared__ LcrCam C_[EPW];
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage_dyn[];   // [4][12 W] (PLANES: [4][12 W + 4 W], colours then segmentation)
+    constexpr int WPE = 4 / EPW;   // waves per env
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int e = wave / WPE, wsub = wave % WPE;
+    const int env = blockIdx.x * EPW + e;
+    const bool live = env < P.n;   // (a ragged batch: the waves of the missing envs only keep the barriers company)
+    Scene &S = S_[e];
+    const int tl = EPW == 1 ? (int)threadIdx.x : (int)threadIdx.x & (64 * WPE - 1);   // thread within its env's waves
+    [[maybe_unused]] const LcrLookVar *LV = nullptr;
+    if (LOOK && live) LV = LK.var + __builtin_amdgcn_readfirstlane(LK.variant[env]);
+    if (tl == 0 && live) {
+        ArmFrames F;
+        build_scene(P, env, S);
+        wrist_frames(P, env, F);
+        if (LOOK) apply_look(LK, *LV, env, P.n, P.task, P.has_target, S.bcol);
+        wrist_camera(F, WR.mount, C_[e]);
+    }
+    __syncthreads();
+    if (tl < NPRIM && live) build_prim(C_[e], 0, W, H, S, tl);
+    __syncthreads();
+    if (!live) return;
+    // the camera and the light: wave-uniform values
+    auto uni = [](float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+    LcrCam C;
+    C.px = uni(C_[e].px); C.py = uni(C_[e].py); C.pz = uni(C_[e].pz);
+    C.xx = uni(C_[e].xx); C.xy = uni(C_[e].xy); C.xz = uni(C_[e].xz); C.yx = uni(C_[e].yx); C.yy = uni(C_[e].yy); C.yz = uni(C_[e].yz);
+    C.zx = uni(C_[e].zx); C.zy = uni(C_[e].zy); C.zz = uni(C_[e].zz); C.s = uni(C_[e].s);
+    const Shade h = LOOK ? look_shade(*LV) : default_shade();
+    unsigned char *st = stage_dyn + wave * (PLANES ? 16 * W : 12 * W);
+    unsigned char *sgst = st + 4 * RB;   // PLANES: the staged segmentation band
+    const int marker = __builtin_amdgcn_readfirstlane(S.marker);
+    const int tx = lane & 15, ty = lane >> 4;   // pixel of this lane inside a 16 x 4 tile
+    const float *cull = S.cull[0][lane < NPRIM ? lane : 0];   // culling: one primitive per lane
+    const size_t plane_px = (size_t)H * W;
+    u32x4 *out = reinterpret_cast<u32x4 *>(WR.img + (size_t)env * plane_px * 3);
+    float *dplane = PLANES && WR.depth ? WR.depth + (size_t)env * plane_px : nullptr;
+    u32x4 *splane = PLANES && WR.seg ? reinterpret_cast<u32x4 *>(WR.seg + (size_t)env * plane_px) : nullptr;
+    for (int b = wsub; b < NB; b += WPE) {
+        const int row0 = 4 * b;
+        // the tile columns [ta, tb] this lane's primitive can touch on rows row0 .. row0 + 3 (empty: ta > tb): the interval arithmetic of lcr_render_obs_kernel
+        const f32x4 cb = *reinterpret_cast<const f32x4 *>(cull);   // y0 y1 x0 x1
+        const bool in_band = lane < NPRIM && (float)(row0 + 3) >= cb.x && (float)row0 <= cb.y;
+        int ta = 1 << 20, tb = -1;
+        if (in_band) {
+            float xa = cb.z, xb = cb.w;
+            if (lane < NARM) {
+                const f32x4 cs = *reinterpret_cast<const f32x4 *>(cull + 4), ct = *reinterpret_cast<const f32x4 *>(cull + 8);
+                const float au = cs.x, av = cs.y, du = cs.z, R = cs.w, slope = ct.x, inv_dv = ct.y, strip_hw = ct.z;
+                const bool flat = ct.w != 0.f;
+                const float f0 = (float)row0 - R - av, f1 = (float)(row0 + 3) + R - av;
+                const float sA = f0 * inv_dv, sB = f1 * inv_dv;
+                const float s0 = flat ? 0.f : clampf(fminf(sA, sB), 0.f, 1.f), s1 = flat ? 1.f : clampf(fmaxf(sA, sB), 0.f, 1.f);
+                const float e0 = s0 * du, e1 = s1 * du;
+                const float c0 = fmaf((float)row0 - av, slope, au), c1 = fmaf((float)(row0 + 3) - av, slope, au);
+                xa = fmaxf(fmaxf(au + fminf(e0, e1) - R, fminf(c0, c1) - strip_hw), xa);
+                xb = fminf(fminf(au + fmaxf(e0, e1) + R, fmaxf(c0, c1) + strip_hw), xb);
+            }
+            if (xb >= 0.f && xa <= (float)(W - 1) && xa <= xb) {
+                ta = (int)fmaxf(xa * (1.f / 16.f), 0.f); tb = (int)fminf(xb * (1.f / 16.f), (float)(NT - 1));
+            }
+        }
+        const float sy = -((float)(row0 + ty) + 0.5f - 0.5f * H) * C.s;
+        for (int t = 0; t < NT; t++) {
+            const unsigned m = (unsigned)__ballot(ta <= t && tb >= t);   // (lanes beyond the primitives hold an empty interval)
+            // (a partial last tile column: lanes beyond the row's end follow the wave with the row's last pixel and write nothing)
+            const int pxt = 16 * t + tx, px = min(pxt, W - 1);
+            const float sx = ((float)px + 0.5f - 0.5f * W) * C.s;
+            f3 col;
+            float tnear;
+            unsigned seg;
+            wrist_pixel(C, S.boxc[0], S.bcol, m, marker, sx, sy, h, col, tnear, seg);
+            if (pxt < W) {
+                const unsigned rgb = pack_rgb(col);
+                unsigned char *stpx = st + ty * RB + 3 * px;
+                stpx[0] = (unsigned char)rgb;
+                stpx[1] = (unsigned char)(rgb >> 8);
+                stpx[2] = (unsigned char)(rgb >> 16);
+                if (PLANES) {
+                    if (dplane) __builtin_nontemporal_store(fminf(tnear, WR.far), dplane + (size_t)(row0 + ty) * W + px);
+                    if (splane) sgst[ty * W + px] = (unsigned char)seg;
+                }
+            }
+        }
+        const u32x4 *sv = reinterpret_cast<const u32x4 *>(st);
+        for (int i = lane; i < VB; i += 64) __builtin_nontemporal_store(sv[i], out + (size_t)b * VB + i);
+        if (PLANES && splane) {
+            const u32x4 *sgv = reinterpret_cast<const u32x4 *>(sgst);
+            for (int i = lane; i < VS; i += 64) __builtin_nontemporal_store(sgv[i], splane + (size_t)b * VS + i);
+        }
+    }
+}
+
+// one env through the wrist camera at any size, one thread per pixel, no culling: the sibling of lcr_render_single_kernel / lcr_render_single_planes_kernel.  Any of the
+// three outputs may be null.  look_env >= 0: with the look of env `look_env` of LK (its variant's colours and light, its own colours)
+__global__ __launch_bounds__(256) void lcr_render_single_wrist_kernel(LcrDev P, LcrWristMount M, int env, int W, int H, float far, unsigned char *out, float *depth, unsigned char *seg_out,
+                                                                      LcrLook LK, int look_env, int look_n) {
+    __shared__ Scene S;
+    __shared__ LcrCam C;
+    if (threadIdx.x == 0) {
+        ArmFrames F;
+        build_scene(P, env, S);
+        wrist_frames(P, env, F);
+        if (look_env >= 0) apply_look(LK, LK.var[LK.variant[look_env]], look_env, look_n, P.task, P.has_target, S.bcol);
+        wrist_camera(F, M, C);
+    }
+    __syncthreads();
+    if (threadIdx.x < NBOX && (int)threadIdx.x < S.nbox)
+        box_consts(C, S.bc[threadIdx.x], S.bX[threadIdx.x], S.bY[threadIdx.x], S.bZ[threadIdx.x], S.bh[threadIdx.x], S.balpha[threadIdx.x], S.boxc[0][threadIdx.x]);
+    __syncthreads();
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= W * H) return;
+    const int v = pix / W, u = pix - v * W;
+    const float sx = (u + 0.5f - 0.5f * W) * C.s, sy = -(v + 0.5f - 0.5f * H) * C.s;
+    const Shade h = look_env >= 0 ? look_shade(LK.var[LK.variant[look_env]]) : default_shade();
+    f3 col;
+    float t;
+    unsigned seg;
+    wrist_pixel(C, S.boxc[0], S.bcol, (1u << S.nbox) - 1u, S.marker, sx, sy, h, col, t, seg);
+    if (out) {
+        const unsigned rgb = pack_rgb(col);
+        out[3 * (size_t)pix + 0] = (unsigned char)rgb;
+        out[3 * (size_t)pix + 1] = (unsigned char)(rgb >> 8);
+        out[3 * (size_t)pix + 2] = (unsigned char)(rgb >> 16);
+    }
+    if (depth) depth[pix] = fminf(t, far);
+    if (seg_out) seg_out[pix] = (unsigned char)seg;
 }
 #endif
 
@@ -967,6 +1189,39 @@ int lcr_launch_render_bg(const LcrDev &P, const LcrCam &front, const LcrCam &top
 
 int lcr_launch_render_single(const LcrDev &P, const LcrCam &cam, int env, int W, int H, unsigned char *out_dev, void *stream) {
     hipLaunchKernelGGL(lcr_render_single_kernel, dim3((W * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, cam, env, W, H, out_dev);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+#endif
+
+#if LCR_RENDER_WRIST
+namespace {
+template <bool PLANES, bool LOOK>
+void launch_wrist(const LcrDev &P, const LcrWrist &WR, const LcrLook &LK, void *stream) {
+    const int epw = P.img_epw;
+    const size_t lds = (size_t)4 * (PLANES ? 16 : 12) * P.img_w;
+    if (epw == 4) hipLaunchKernelGGL((lcr_render_wrist_kernel<PLANES, LOOK, 4>), dim3((P.n + 3) / 4), dim3(256), lds, (hipStream_t)stream, P, WR, LK);
+    else if (epw == 2) hipLaunchKernelGGL((lcr_render_wrist_kernel<PLANES, LOOK, 2>), dim3((P.n + 1) / 2), dim3(256), lds, (hipStream_t)stream, P, WR, LK);
+    else hipLaunchKernelGGL((lcr_render_wrist_kernel<PLANES, LOOK, 1>), dim3(P.n), dim3(256), lds, (hipStream_t)stream, P, WR, LK);
+}
+}  // namespace
+
+// the batched wrist frames (+ the planes WR points at; LK: with the envs' looks): the mapping by frame size of the two-camera frame kernel (P.img_epw)
+int lcr_launch_render_wrist(const LcrDev &P, const LcrWrist &WR, const LcrLook *LK, void *stream) {
+    if (!WR.img || (LK && (!LK->var || !LK->variant || !LK->rgb))) return (int)hipErrorInvalidValue;
+    const bool planes = WR.depth || WR.seg;
+    const LcrLook none{};
+    if (LK) { if (planes) launch_wrist<true, true>(P, WR, *LK, stream); else launch_wrist<false, true>(P, WR, *LK, stream); }
+    else { if (planes) launch_wrist<true, false>(P, WR, none, stream); else launch_wrist<false, false>(P, WR, none, stream); }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lcr_launch_render_single_wrist(const LcrDev &P, const LcrWristMount &M, int env, int W, int H, float far, unsigned char *rgb_dev, float *depth_dev, unsigned char *seg_dev,
+                                   const LcrLook *LK, int look_env, int look_n, void *stream) {
+    const LcrLook none{};
+    hipLaunchKernelGGL(lcr_render_single_wrist_kernel, dim3((W * H + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, M, env, W, H, far, rgb_dev, depth_dev, seg_dev,
+                       LK ? *LK : none, LK ? look_env : -1, look_n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -4,6 +4,7 @@
     one file per episode  "{name_prefix}-episode-{id}.hdf5"  with datasets
         observations/images/front   (T, H, W, 3) uint8          <- obs["image_front"]   (H x W: 240 x 320 unless the env was given an image_size)
         observations/images/top     (T, H, W, 3) uint8          <- obs["image_top"]
+        observations/images/wrist   (T, H, W, 3) uint8          <- obs["image_wrist"]   (only when the env has a wrist camera; the reference has none)
         observations/qpos           (T, 6) float32               <- obs["arm_qpos"]
         observations/qvel           (T, 6) float32               <- obs["arm_qvel"]
         action                      (T, k) float32
@@ -29,6 +30,7 @@ except Exception:
     h5py = None
 
 DATASETS = ("observations/images/front", "observations/images/top", "observations/qpos", "observations/qvel", "action")
+OPTIONAL_DATASETS = ("observations/images/wrist",)   # written when the observations carry them
 
 
 def backend():
@@ -48,6 +50,8 @@ def write_episode(path_hdf5, observations, actions):
     if "image_front" in observations[0]:
         data["observations/images/front"] = np.stack([o["image_front"] for o in observations])
         data["observations/images/top"] = np.stack([o["image_top"] for o in observations])
+    if "image_wrist" in observations[0]:
+        data["observations/images/wrist"] = np.stack([o["image_wrist"] for o in observations])
     if h5py is not None:
         with h5py.File(path_hdf5, "w") as f:
             for k, v in data.items():
@@ -66,8 +70,8 @@ def load_episode(path):
             return {k: z[k] for k in z.files}
     if h5py is not None:  # pragma: no cover
         with h5py.File(path, "r") as f:
-            return {k: f[k][()] for k in DATASETS if k in f}
-    return _hdf5c.read_file(path, DATASETS)
+            return {k: f[k][()] for k in DATASETS + OPTIONAL_DATASETS if k in f}
+    return _hdf5c.read_file(path, DATASETS + OPTIONAL_DATASETS)
 
 
 def hdf5_selftest():
@@ -173,6 +177,9 @@ class VecRecorder:
         if has_img:
             front = sim.read_rows(sim.image_front, self.which)
             top = sim.read_rows(sim.image_top, self.which)
+        has_wrist = has_img and sim.image_wrist is not None
+        if has_wrist:
+            wrist = sim.read_rows(sim.image_wrist, self.which)
         tq = None
         for j, e in enumerate(self.which):
             if h["did_reset"][e]:
@@ -191,10 +198,14 @@ class VecRecorder:
                     ih, iw = sim.image_size
                     o["image_front"] = sim.render_state(qpos, tgt, "camera_front", iw, ih)
                     o["image_top"] = sim.render_state(qpos, tgt, "camera_top", iw, ih)
+                    if has_wrist:
+                        o["image_wrist"] = sim.render_state(qpos, tgt, "camera_wrist", iw, ih)
             else:
                 o = {"arm_qpos": h["arm_qpos"][e].copy(), "arm_qvel": h["arm_qvel"][e].copy()}
                 if has_img:
                     o["image_front"], o["image_top"] = front[j], top[j]
+                    if has_wrist:
+                        o["image_wrist"] = wrist[j]
             self._obs[e].append(o)
             self._act[e].append(np.asarray(actions[e], np.float32))
             if h["did_reset"][e]:

@@ -53,6 +53,8 @@ def _obs_spaces(sim, observation_mode):
     if observation_mode in ("image", "both"):
         subs["image_front"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)   # (240, 320, 3) unless VecSim was given an image_size
         subs["image_top"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)
+        if sim.image_wrist is not None:   # VecSim(wrist_camera=...): the link-mounted third camera
+            subs["image_wrist"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)
         for k in sim.plane_arrays():   # VecSim(image_planes=...): depth_front / depth_top in metres up to depth_far, segmentation_front / segmentation_top ids (include/lcr.h)
             subs[k] = sp.Box(0.0, sim.depth_far, shape=sim.image_size, dtype=np.float32) if k.startswith("depth_") else sp.Box(0, 255, shape=sim.image_size, dtype=np.uint8)
     if observation_mode in ("state", "both"):
@@ -91,6 +93,8 @@ class LowCostRobotVecEnv(_SB3VecEnv):
         if self.observation_mode in ("image", "both"):
             o["image_front"] = sim.image_front.numpy()
             o["image_top"] = sim.image_top.numpy()
+            if sim.image_wrist is not None:
+                o["image_wrist"] = sim.image_wrist.numpy()
             for k, a in sim.plane_arrays().items():
                 o[k] = a.numpy()
         # forced copies: the pinned mirror is overwritten by the next fetch and freed by close(), and SB3 keeps the returned arrays
@@ -115,6 +119,8 @@ class LowCostRobotVecEnv(_SB3VecEnv):
             fr, tp = sim.render_terminal(env_ids)
             if sim.image_planes:
                 planes = sim.render_terminal_planes(env_ids)
+            if sim.image_wrist is not None:   # (image_wrist and, with planes, depth_wrist / segmentation_wrist)
+                planes = {**planes, **sim.render_terminal_wrist(env_ids)}
         out = []
         for j, t in enumerate(tobs_rows):
             d = {"arm_qpos": t[0:6].copy(), "arm_qvel": t[6:12].copy()}
@@ -276,12 +282,17 @@ class LowCostRobotVectorEnv:
                 ridx = np.nonzero(h["did_reset"])[0]
                 fin["image_front"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)   # (calloc'ed: pages of envs that were not reset are never touched)
                 fin["image_top"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)
+                if sim.image_wrist is not None:
+                    fin["image_wrist"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)
                 for k, a in sim.plane_arrays().items():
                     fin[k] = np.zeros((self.num_envs,) + sim.image_size, a.dtype)
                 if ridx.size:
                     fin["image_front"][ridx], fin["image_top"][ridx] = sim.render_terminal(ridx)
                     if sim.image_planes:
                         for k, a in sim.render_terminal_planes(ridx).items():
+                            fin[k][ridx] = a
+                    if sim.image_wrist is not None:
+                        for k, a in sim.render_terminal_wrist(ridx).items():
                             fin[k][ridx] = a
             fin = {k: fin[k] for k in v._keys}
             infos["final_obs"] = fin

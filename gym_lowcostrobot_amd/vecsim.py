@@ -12,7 +12,7 @@ import numpy as np
 from . import _capi
 from ._capi import ACTION_MODES, OBS_MODES, REWARD_TYPES, TASKS, LcrConfig, LcrHostView, LcrObsView, LcrOutView, LcrPlanesView, check
 
-CAMERAS = {"camera_front": 0, "camera_top": 1, "camera_vizu": 2}
+CAMERAS = {"camera_front": 0, "camera_top": 1, "camera_vizu": 2, "camera_wrist": 3}   # (camera_wrist: on a sim with a wrist camera)
 
 
 def _vp(a):
@@ -92,6 +92,7 @@ class VecSim:
         depth_far=10.0,
         look_variants=None,
         look_sampler=None,
+        wrist_camera=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -120,6 +121,15 @@ class VecSim:
                 raise ValueError("look_variants need image observations: observation_mode 'image' or 'both'")
             look_variants = [_capi.LookVariant.from_any(v) for v in look_variants]
             look_sampler = None if look_sampler is None else _capi.LookSampler.from_any(look_sampler)
+        # the wrist camera (lcr_enable_wrist_camera): None / False = none, True = the default mount, or a dict of link / pos / xyaxes / fovy_deg over it.  The library checks
+        # the mount itself here, without a handle (lcr_wrist_camera_check), as it does again when it is enabled
+        if wrist_camera is None or wrist_camera is False:
+            wrist_camera = None
+        else:
+            if observation_mode == "state":
+                raise ValueError("wrist_camera needs image observations: observation_mode 'image' or 'both'")
+            wrist_camera = _capi.WristCamera.from_any(wrist_camera)
+            check(self.L.lcr_wrist_camera_check(ctypes.byref(wrist_camera)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -224,6 +234,18 @@ class VecSim:
             except Exception:
                 self.close()
                 raise
+        self.wrist_camera = None
+        self.image_wrist = self.depth_wrist = self.seg_wrist = None
+        if wrist_camera is not None:   # (before the planes: planes enabled afterwards cover the wrist camera)
+            try:
+                check(self.L.lcr_enable_wrist_camera(self.handle, ctypes.byref(wrist_camera)))
+                wv = _capi.LcrWristView()
+                check(self.L.lcr_get_wrist_camera(self.handle, ctypes.byref(wv)))
+            except Exception:
+                self.close()
+                raise
+            self.wrist_camera = wv.camera.as_dict()
+            self.image_wrist = DeviceArray(self, wv.image_wrist, img, np.uint8)
         self.image_planes, self.depth_far = image_planes, depth_far
         self.depth_front = self.depth_top = self.seg_front = self.seg_top = None
         if image_planes:
@@ -240,6 +262,11 @@ class VecSim:
             self.depth_top = DeviceArray(self, pv.depth_top, pl, np.float32) if pv.depth_top else None
             self.seg_front = DeviceArray(self, pv.seg_front, pl, np.uint8) if pv.seg_front else None
             self.seg_top = DeviceArray(self, pv.seg_top, pl, np.uint8) if pv.seg_top else None
+            if self.wrist_camera is not None:
+                wv = _capi.LcrWristView()
+                check(self.L.lcr_get_wrist_camera(self.handle, ctypes.byref(wv)))
+                self.depth_wrist = DeviceArray(self, wv.depth_wrist, pl, np.float32) if wv.depth_wrist else None
+                self.seg_wrist = DeviceArray(self, wv.seg_wrist, pl, np.uint8) if wv.seg_wrist else None
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -311,15 +338,15 @@ class VecSim:
         check(self.L.lcr_fill_random_actions(self.handle, ctypes.c_void_p(arr.ptr), int(seed), int(step)))
 
     def render(self, env=0, camera="camera_vizu", width=640, height=640):
-        """ray-cast one env: camera_front / camera_top / camera_vizu -> (height, width, 3) uint8"""
-        cam = {"camera_front": 0, "camera_top": 1, "camera_vizu": 2}[camera]
+        """ray-cast one env: camera_front / camera_top / camera_vizu (camera_wrist on a sim that has one) -> (height, width, 3) uint8"""
+        cam = CAMERAS[camera]
         out = np.empty((height, width, 3), np.uint8)
         check(self.L.lcr_render(self.handle, int(env), cam, int(width), int(height), _vp(out)))
         return out
 
     def render_state(self, qpos, target=None, camera="camera_front", width=320, height=240):
         """ray-cast an arbitrary pose (qpos of length nq as env.data.qpos; target_pos or None) without touching the sim state"""
-        cam = {"camera_front": 0, "camera_top": 1, "camera_vizu": 2}[camera]
+        cam = CAMERAS[camera]
         q = np.ascontiguousarray(qpos, np.float64)
         if q.shape != (self.nq,):
             raise ValueError(f"qpos must have shape ({self.nq},)")
@@ -338,6 +365,26 @@ class VecSim:
         top = np.empty_like(front)
         check(self.L.lcr_render_terminal(self.handle, _vp(ids), int(ids.size), _vp(front), _vp(top)))
         return front, top
+
+    def render_terminal_wrist(self, env_ids):
+        """the last wrist frames of the episodes the last step ended in the listed envs, one batch (the sibling of render_terminal(), same precondition): a dict with the
+        keys of observations() -- image_wrist (len(env_ids), H, W, 3) uint8 and, with image_planes, depth_wrist float32 / segmentation_wrist uint8 (len(env_ids), H, W)"""
+        if self.wrist_camera is None:
+            raise ValueError("render_terminal_wrist: no wrist_camera is enabled")
+        ids = np.ascontiguousarray(env_ids, np.int32)
+        if ids.size and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():
+            raise ValueError("render_terminal_wrist: every listed env must have finished an episode in the last step (did_reset)")
+        shape = (ids.size,) + self.image_size
+        rgb = np.empty(shape + (3,), np.uint8)
+        d = np.empty(shape, np.float32) if self.depth_wrist is not None else None
+        s = np.empty(shape, np.uint8) if self.seg_wrist is not None else None
+        check(self.L.lcr_render_terminal_wrist(self.handle, _vp(ids), int(ids.size), _vp(rgb), _vp(d), _vp(s)))
+        out = {"image_wrist": rgb}
+        if d is not None:
+            out["depth_wrist"] = d
+        if s is not None:
+            out["segmentation_wrist"] = s
+        return out
 
     def look(self):
         """the looks of the envs (lcr_get_look): {"variants": the handle's list of LookVariant, "variant": (N,) int32, "rgb": (9, N) float32 -- cube, second cube, marker --,
@@ -406,6 +453,10 @@ class VecSim:
             out["depth_front"], out["depth_top"] = self.depth_front, self.depth_top
         if self.seg_front is not None:
             out["segmentation_front"], out["segmentation_top"] = self.seg_front, self.seg_top
+        if self.depth_wrist is not None:   # (behind the four keys of the two scene cameras, which keep their places)
+            out["depth_wrist"] = self.depth_wrist
+        if self.seg_wrist is not None:
+            out["segmentation_wrist"] = self.seg_wrist
         return out
 
     def read_rows(self, arr, rows):
@@ -449,6 +500,8 @@ class VecSim:
         if self.image_front is not None:
             obs["image_front"] = self.image_front.numpy()
             obs["image_top"] = self.image_top.numpy()
+            if self.image_wrist is not None:
+                obs["image_wrist"] = self.image_wrist.numpy()
             for k, a in self.plane_arrays().items():
                 obs[k] = a.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:

@@ -313,7 +313,7 @@ int lcr_fill_random_actions(lcr_sim *sim, float *action_dev, uint64_t seed, uint
 /* == render() with render_mode="rgb_array" (reach_cube_env.py:350-355: 640x640 frame of camera_vizu) and ad-hoc frames of
  * the observation cameras: ray-cast env `env` from camera 0 (camera_front), 1 (camera_top) or 2 (camera_vizu) at
  * width x height into rgb_host[height][width][3].  Synchronous. */
-int lcr_render(lcr_sim *sim, int env, int camera, int width, int height, uint8_t *rgb_host);
+int lcr_render(lcr_sim *sim, int env, int camera, int width, int height, uint8_t *rgb_host);   /* (camera 3: the wrist camera, on a handle that has one -- see lcr_enable_wrist_camera) */
 /* The same for an arbitrary pose given by the caller (qpos_host[nq] as env.data.qpos, target_host[3] or NULL): e.g. the last
  * frame of an episode whose env the step kernel has already reset (terminal_obs + terminal_quat).  Does not touch the sim state. */
 int lcr_render_state(lcr_sim *sim, int camera, int width, int height, const double *qpos_host, const float *target_host, uint8_t *rgb_host);
@@ -405,6 +405,57 @@ int lcr_enable_look(lcr_sim *sim, int n_variants, const lcr_look_variant *varian
  * the values of the masked envs are checked (variant in [0, n_variants), colours in [0, 1]); redraws the frames as a masked lcr_reset does.  Synchronous. */
 int lcr_set_look(lcr_sim *sim, const uint8_t *mask_host, const int32_t *variant_host /*[N]*/, const float *rgb_host /*[9][N]: cube, cube2, marker*/);
 int lcr_get_look(lcr_sim *sim, int32_t *variant /*[N]*/, float *rgb /*[9][N]*/, uint32_t *episode /*[N]*/);   /* any may be NULL */
+
+/* == The wrist camera: an optional third observation camera per handle, rigidly mounted on a body of the arm (or fixed in the world), drawn for every env beside
+ * camera_front / camera_top at the handle's frame size -- the eye-in-hand view a visuomotor policy for this arm is normally fed; the reference's scenes have the two fixed
+ * cameras only.  Off by default: without lcr_enable_wrist_camera no frame, plane, state or output of the handle changes.
+ *   axes    built in fp64 on the host: X normalised; Y minus its projection on X, normalised (Gram-Schmidt, as MuJoCo does for xyaxes); Z = X x Y; then rounded to float32.
+ *   pose    per env and step, from the chain of link frames that places the arm's boxes: ro = p_link + R_link pos, X_w = R_link X (likewise Y, Z); link 0: the numbers themselves.
+ *   rays    s = 2 tan(fovy / 2) / H in fp64, rounded; d = sx X_w + sy Y_w - Z_w with sx, sy as the other cameras have them.
+ *   scene, shading, marker blending, depth (t along the un-normalised ray) and segmentation ids (0 .. 10, bit 7 the marker): exactly those of the other cameras; the
+ *           headlight is at the camera.  A box that contains the camera is not seen (t > 0).
+ *   floor   seen only where the normalised d.z < -1e-6 AND ro.z > 0.  A camera at or below the floor plane -- random arm poses do put a camera on link_5 there -- sees no
+ *           floor: those rays take the sky formula (a = clamp(2 normalised d.z, 0, 1): sky_rgb where they point down), segmentation 0, depth depth_far, and the floor
+ *           limits no box.
+ *   look    the wrist frames take the env's variant's floor, sky, light and arm colours and the env's own nine channels; the variant's camera offsets do not apply to it.
+ *   order   look and wrist camera in either order, the planes last: planes enabled afterwards cover the wrist camera (depth_wrist / seg_wrist, [N][H][W]). */
+typedef struct lcr_wrist_camera {
+    int32_t link;      /* 0 = world frame (a fixed third camera); 1..6 = body frame of link_1..link_6 (follower.xml:56-93) */
+    float pos[3];      /* metres in that frame; each |.| <= 0.5 (link 0: <= 2, and pos[2] >= 0.05) */
+    float xyaxes[6];   /* MuJoCo's camera xyaxes in that frame: X then Y; the camera looks along -Z, Z = X x Y */
+    float fovy_deg;    /* [20, 120] */
+} lcr_wrist_camera;
+typedef struct lcr_wrist_view {
+    int32_t enabled;                   /* 0: no wrist camera, everything below is 0 / NULL */
+    lcr_wrist_camera camera;           /* the arguments of lcr_enable_wrist_camera */
+    int32_t image_width, image_height;
+    float depth_far;                   /* the planes' far clip, 0 without planes */
+    const uint8_t *image_wrist;        /* device, [N][H][W][3] */
+    const float *depth_wrist;          /* device, [N][H][W], or NULL (plane not enabled) */
+    const uint8_t *seg_wrist;          /* device, [N][H][W], or NULL */
+} lcr_wrist_view;
+/* Guard regions.  The wrist frames lie between two regions of LCR_WRIST_GUARD bytes, [image_wrist - LCR_WRIST_GUARD, image_wrist) and LCR_WRIST_GUARD bytes from the first 256-byte
+ * boundary at or behind the frames' end; depth_wrist and seg_wrist each have LCR_WRIST_GUARD bytes before them and behind their end rounded up likewise.  The regions are filled
+ * with LCR_WRIST_GUARD_BYTE when the buffers are allocated and nothing writes them afterwards: a caller (the tests do) can read them back to see that the kernels keep to their frames. */
+#define LCR_WRIST_GUARD 4096
+#define LCR_WRIST_GUARD_BYTE 0xA5
+/* link 5, pos (0.03, 0.0033, 0.045), xyaxes (0, 1, 0, -0.4226, 0, 0.9063), fovy 60: above the gripper body, looking 25 degrees down along its -x towards the end-effector site */
+int lcr_wrist_camera_default(lcr_wrist_camera *cam);
+/* The checks lcr_enable_wrist_camera makes of `cam` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field's name in the message */
+int lcr_wrist_camera_check(const lcr_wrist_camera *cam);
+/* Switch the wrist camera on.  `cam` is checked before the handle is looked at (LCR_ERR_INVALID with the field's name in the message: link outside 0 .. 6, pos out of
+ * range, a zero X or a Y parallel to X -- norm after the projection < 1e-6 --, fovy_deg outside [20, 120], a number that is not finite); then a NULL handle, a handle without
+ * image observations and a handle whose planes are already enabled are refused.  Allocates [N][H][W][3] and draws it from the current state; from then on whatever draws the
+ * two colour frames -- step, reset and its masked no-op form, lcr_set_look -- draws the wrist frames behind them, on the same stream, from the same pose snapshot.  Fixed for
+ * the life of the handle: the same arguments again do nothing, other arguments are refused. */
+int lcr_enable_wrist_camera(lcr_sim *sim, const lcr_wrist_camera *cam);
+/* The wrist camera's buffers; waits (on the handle's stream) for frames still being ray-cast on the second stream, as every entry point but the step does. */
+int lcr_get_wrist_camera(lcr_sim *sim, lcr_wrist_view *out);
+/* On a handle with a wrist camera lcr_render, lcr_render_state, lcr_render_planes and lcr_render_state_planes accept camera 3: the wrist camera of env `env`'s pose, or of
+ * the given pose, at any size.  On any other handle 3 is refused.
+ * The batched last wrist frames of finished episodes: the sibling of lcr_render_terminal (same precondition, same terminal look), rgb_host [count][H][W][3]; depth_host /
+ * seg_host [count][H][W] may be NULL, and must be where that plane is not enabled. */
+int lcr_render_terminal_wrist(lcr_sim *sim, const int32_t *env_ids_host, int count, uint8_t *rgb_host, float *depth_or_null, uint8_t *seg_or_null);
 
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n

@@ -1,5 +1,5 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]]
+    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
@@ -9,6 +9,9 @@ per pixel, so a store-bound kernel would take 7/3, 4/3 and 8/3 of the plain time
 --look K[,K...] (e.g. --look 1,8,64): ONLY (i), at 240x320 and 84x84, for the build without a look and with a look of K variants (VecSim(look_variants=...): K different
 camera pairs, floors, skies and lights, variants and colours spread over the envs by the sampler): the same bytes are written, what changes is where the untouched bands are copied
 from -- K cached background pairs instead of one.
+--wrist: ONLY the wrist camera (VecSim(wrist_camera=True), the default mount), at 84x84, 128x128 and 240x320, two rounds of [without, with] in turn: (i) of a sim without it
+(the two-camera frame kernel) and of a sim with it (both kernels, back to back on one stream), the wrist kernel's time as the difference of the two, the bytes either kernel
+writes per ms; (ii) env-steps/s closed and open loop, without and with the camera.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -20,14 +23,16 @@ import numpy as np  # noqa: E402
 from gym_lowcostrobot_amd import VecSim  # noqa: E402
 
 PLANES = "--planes" in sys.argv
+WRIST = "--wrist" in sys.argv
 LOOK = [int(k) for k in sys.argv[sys.argv.index("--look") + 1].split(",")] if "--look" in sys.argv else []
-args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--planes", "--look") and sys.argv[i - 1] != "--look"]
+args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--planes", "--look", "--wrist") and sys.argv[i - 1] != "--look"]
 n = int(args[0]) if len(args) > 0 else 32768
 task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
 SOAK_S, WINDOWS, STEPS = 2.0, 7, 60
 print(f"frame sizes: {task}, {n} envs, default preset, LCR_RENDER_EPW={os.environ.get('LCR_RENDER_EPW', '(by frame size)')}")
-print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
+if not WRIST:
+    print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
 rows = []
 
 
@@ -80,6 +85,50 @@ if LOOK:
                   f"{max(K, 1) * 2 * H * W * 3 / 1e6:7.2f} MB", flush=True)
             sim.free(act)
             sim.close()
+    sys.exit(0)
+
+
+def loops(sim, act):
+    """env-steps/s of step + frames: closed loop (a sync after every step) and open loop (steps enqueued back to back)"""
+    sim.sync()
+    t0 = time.perf_counter()
+    for t in range(STEPS):
+        sim.step_device(act[t % 8].ptr)
+        sim.sync()
+    closed = n * STEPS / (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    for t in range(STEPS):
+        sim.step_device(act[t % 8].ptr)
+    sim.sync()
+    return closed, n * STEPS / (time.perf_counter() - t0)
+
+
+if WRIST:
+    print(f"the wrist camera ({n} envs, default mount): ms per launch (median of {WINDOWS} windows of ten; min max), GB / ms = TB/s written, env-steps/s closed / open loop")
+    for H, W in [(84, 84), (128, 128), (240, 320)]:
+        two = wr = None
+        for rnd in (1, 2):
+            for on in (False, True):
+                sim = VecSim(task, n, observation_mode="both", image_size=(H, W), **({"wrist_camera": True} if on else {}))
+                act = [sim.alloc_actions() for _ in range(8)]
+                for t, a in enumerate(act):
+                    sim.fill_random_actions(a, 1, t)
+                for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+                    sim.step_device(act[t % 8].ptr)
+                ms, wmin, wmax = frame_kernel_ms(sim)
+                closed, opened = loops(sim, act)
+                nb = 2 * H * W * 3 * n
+                if not on:
+                    two = ms
+                    print(f"{H:4d}x{W:<4d} round {rnd} two-camera kernel        {ms:7.3f} ({wmin:.3f} {wmax:.3f})  {nb / ms / 1e9:5.2f} TB/s   "
+                          f"steps/s {closed:.3e} / {opened:.3e}", flush=True)
+                else:
+                    wr = ms - two
+                    print(f"{H:4d}x{W:<4d} round {rnd} two-camera + wrist kernel {ms:7.3f} ({wmin:.3f} {wmax:.3f})  wrist kernel (difference) {wr:6.3f} ms  "
+                          f"{nb / 2 / wr / 1e9:5.2f} TB/s   steps/s {closed:.3e} / {opened:.3e}", flush=True)
+                for a in act:
+                    sim.free(a)
+                sim.close()
     sys.exit(0)
 
 plane_rows = []
