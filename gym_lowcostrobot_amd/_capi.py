@@ -31,6 +31,11 @@ IMAGE_PLANES = {"depth": PLANE_DEPTH, "segmentation": PLANE_SEGMENTATION}
 
 LOOK_MAX_VARIANTS = 64   # LCR_LOOK_MAX_VARIANTS
 WRIST_GUARD, WRIST_GUARD_BYTE = 4096, 0xA5   # LCR_WRIST_GUARD, LCR_WRIST_GUARD_BYTE: the guard regions around the wrist camera's buffers
+# the observation stack (lcr_enable_obs_stack): LCR_STACK_CAM_* bits in channel order, lcr_obs_stack_dtype, lcr_obs_stack_fill, LCR_STACK_MAX_FRAMES
+STACK_CAMERAS = {"front": 1, "top": 2, "wrist": 4}
+STACK_DTYPES = {"uint8": 0, "float16": 1, "float32": 2}
+STACK_FILLS = {"repeat": 0, "zero": 1}
+STACK_MAX_FRAMES = 8
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -45,6 +50,7 @@ SYMBOLS = [
     "lcr_enable_image_planes", "lcr_get_image_planes", "lcr_render_planes", "lcr_render_state_planes", "lcr_render_terminal_planes",
     "lcr_look_variant_default", "lcr_enable_look", "lcr_set_look", "lcr_get_look",
     "lcr_wrist_camera_default", "lcr_wrist_camera_check", "lcr_enable_wrist_camera", "lcr_get_wrist_camera", "lcr_render_terminal_wrist",
+    "lcr_obs_stack_check", "lcr_enable_obs_stack", "lcr_get_obs_stack",
 ]
 
 
@@ -245,6 +251,68 @@ class LcrWristView(ctypes.Structure):
     ]
 
 
+class ObsStackSpec(ctypes.Structure):
+    """lcr_obs_stack_spec: depth, cameras, element type and refill rule of the observation stack (include/lcr.h)"""
+    _fields_ = [
+        ("frames", ctypes.c_int32),      # K, 1 .. 8
+        ("cameras", ctypes.c_uint32),    # STACK_CAMERAS bits; 0 = every camera the handle has
+        ("dtype", ctypes.c_int32),       # STACK_DTYPES
+        ("reset_fill", ctypes.c_int32),  # STACK_FILLS
+    ]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b),
+                "dtype": {v: k for k, v in STACK_DTYPES.items()}[int(self.dtype)], "reset_fill": {v: k for k, v in STACK_FILLS.items()}[int(self.reset_fill)]}
+
+    @classmethod
+    def from_any(cls, v):
+        """an ObsStackSpec, an int (that many frames of every camera, uint8, repeat), or a dict of some of frames / cameras / dtype / reset_fill"""
+        import numpy as np
+
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer, dict)):
+            raise ValueError(f"obs_stack must be None, a number of frames or a dict of frames / cameras / dtype / reset_fill, got {v!r}")
+        v = {"frames": v} if not isinstance(v, dict) else dict(v)
+        out = cls(frames=1)
+        frames = v.pop("frames", 1)
+        if isinstance(frames, (bool, np.bool_)) or not isinstance(frames, (int, np.integer)) or not 1 <= frames <= STACK_MAX_FRAMES:
+            raise ValueError(f"obs_stack: frames must be an integer in 1 .. {STACK_MAX_FRAMES}, got {frames!r}")
+        out.frames = int(frames)
+        cams = v.pop("cameras", None)
+        if cams is not None:
+            if isinstance(cams, str) or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"obs_stack: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        dtype = v.pop("dtype", "uint8")
+        try:
+            dtype = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        except TypeError:
+            pass
+        if dtype not in STACK_DTYPES:
+            raise ValueError(f"obs_stack: dtype must be 'uint8', 'float16' or 'float32', got {dtype!r}")
+        out.dtype = STACK_DTYPES[dtype]
+        fill = v.pop("reset_fill", "repeat")
+        if fill not in STACK_FILLS:
+            raise ValueError(f"obs_stack: reset_fill must be 'repeat' or 'zero', got {fill!r}")
+        out.reset_fill = STACK_FILLS[fill]
+        if v:
+            raise ValueError(f"unknown obs_stack fields {sorted(v)}")
+        return out
+
+
+class LcrObsStackView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", ObsStackSpec),          # cameras resolved to the bits in use
+        ("channels", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("data", ctypes.c_void_p),       # [N][K][C][H][W] of the element type
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -366,6 +434,9 @@ def load():
     L.lcr_enable_wrist_camera.argtypes = [vp, ctypes.POINTER(WristCamera)]
     L.lcr_get_wrist_camera.argtypes = [vp, ctypes.POINTER(LcrWristView)]
     L.lcr_render_terminal_wrist.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+    L.lcr_obs_stack_check.argtypes = [ctypes.POINTER(ObsStackSpec)]
+    L.lcr_enable_obs_stack.argtypes = [vp, ctypes.POINTER(ObsStackSpec)]
+    L.lcr_get_obs_stack.argtypes = [vp, ctypes.POINTER(LcrObsStackView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

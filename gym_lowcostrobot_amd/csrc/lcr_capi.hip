@@ -13,6 +13,7 @@
 #include "../../include/lcr.h"
 #include "lcr_device.h"
 #include "lcr_model_gen.h"
+#include "lcr_stack.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -143,6 +144,13 @@ struct lcr_sim {
     lcr_wrist_camera wrist_cam;  // the arguments of lcr_enable_wrist_camera
     LcrWrist wrist;              // the arguments of the kernels that draw it
     void *wrist_mem;
+    // the observation stack (lcr_enable_obs_stack): one allocation -- guard, stack, guard, the two snapshots of did_reset --, fixed for the life of the handle
+    bool stack_on;
+    lcr_obs_stack_spec stack_spec;     // as enabled, cameras resolved
+    LcrStack stack;                    // the arguments of its kernel (flags and op are set per launch)
+    void *stack_mem;
+    size_t stack_bytes_per_env;
+    unsigned char *snap_reset[2];      // beside snap_qpos / snap_target / snap_look
 };
 
 // whatever draws the handle's colour frames draws its enabled planes in the same launch
@@ -168,6 +176,13 @@ static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const 
     else rc = lcr_launch_render_obs(P, s->cam_front, s->cam_top, stream);
     if (!rc && s->wrist_on) rc = launch_wrist_frames(s, P, stream, look);
     return rc;
+}
+
+// the stack kernel, behind the frame kernels on their stream: envs with flags[e] != 0 are refilled, `op` (LCR_STACK_*) is what happens to the others (flags null: to all)
+static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *flags, int op) {
+    LcrStack A = s->stack;
+    A.flags = flags; A.op = op;
+    return lcr_launch_obs_stack(A, stream);
 }
 
 // the wrist camera's mount with the ray scale of a frame `height` rows high (s = 2 tan(fovy / 2) / height in fp64, then rounded)
@@ -596,6 +611,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->planes_mem) (void)hipFree(s->planes_mem);
     if (s->look_mem) (void)hipFree(s->look_mem);
     if (s->wrist_mem) (void)hipFree(s->wrist_mem);
+    if (s->stack_mem) (void)hipFree(s->stack_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -641,6 +657,10 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
     if (s->has_images) {
         rc = launch_frames(s, s->dev, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (s->stack_on) {   // masked envs (no mask: all) are refilled, the others have their newest slot rewritten
+            rc = launch_stack(s, s->stream, mask_host ? s->mask_dev : nullptr, mask_host ? LCR_STACK_NEWEST : LCR_STACK_REFILL);
+            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
+        }
     }
     // the staging copies above read caller memory: do not return before they are consumed
     if (mask_host || seeds_host) HIPCHK(hipStreamSynchronize(s->stream));
@@ -666,17 +686,27 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         HIPCHK(hipMemcpyAsync(s->snap_target[p], s->dev.target, sizeof(float) * 3 * N, hipMemcpyDeviceToDevice, s->stream));
         // (and the looks, 40 B per env: the redraw of the next step must not reach the frames of this one)
         if (s->look_K) HIPCHK(hipMemcpyAsync(s->snap_look[p], s->look_cur, sizeof(int) * 10 * N, hipMemcpyDeviceToDevice, s->stream));
+        // (and did_reset, 1 B per env, for the stack: the step kernel of the next step overwrites the flags while the stack of this one may still have to read them)
+        if (s->stack_on) HIPCHK(hipMemcpyAsync(s->snap_reset[p], s->dev.did_reset, N, hipMemcpyDeviceToDevice, s->stream));
         HIPCHK(hipEventRecord(s->ev_snap[p], s->stream));
         HIPCHK(hipStreamWaitEvent(s->rstream, s->ev_snap[p], 0));
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
         rc = launch_frames(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (s->stack_on) {   // before ev_rdone: join_render then covers the stack as it covers the frames
+            rc = launch_stack(s, s->rstream, s->snap_reset[p], LCR_STACK_PUSH);
+            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
+        }
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
     } else if (s->has_images) {
         rc = launch_frames(s, s->dev, s->stream);
         if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (s->stack_on) {   // same stream as the step kernel: did_reset itself is current until the next step
+            rc = launch_stack(s, s->stream, s->dev.did_reset, LCR_STACK_PUSH);
+            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
+        }
     }
     return LCR_OK;
 }
@@ -1281,6 +1311,7 @@ int lcr_enable_look(lcr_sim *s, int n_variants, const lcr_look_variant *variants
         if (same) return LCR_OK;
         return fail(LCR_ERR_INVALID, "a look of %d variants is enabled already and fixed for the life of the handle", s->look_K);
     }
+    if (s->stack_on) return fail(LCR_ERR_INVALID, "the observation stack is enabled already: enable the look first and the stack last");
     if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the look first and the planes second (their cached backgrounds are drawn per variant)");
 
     const size_t N = (size_t)s->dev.n, img = (size_t)s->dev.img_h * s->dev.img_w * 3, K = (size_t)n_variants;
@@ -1384,6 +1415,10 @@ int lcr_set_look(lcr_sim *s, const uint8_t *mask_host, const int32_t *variant_ho
     HIPCHK(hipMemcpy(s->look_cur, cur.data(), sizeof(int) * 10 * N, hipMemcpyHostToDevice));
     int rc = launch_frames(s, s->dev, s->stream);
     if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (s->stack_on) {   // no time has passed: the newest slot of every env is rewritten
+        rc = launch_stack(s, s->stream, nullptr, LCR_STACK_NEWEST);
+        if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
+    }
     HIPCHK(hipStreamSynchronize(s->stream));
     return LCR_OK;
 }
@@ -1458,6 +1493,7 @@ int lcr_enable_wrist_camera(lcr_sim *s, const lcr_wrist_camera *cam) {
         if (memcmp(&s->wrist_cam, cam, sizeof *cam) == 0) return LCR_OK;
         return fail(LCR_ERR_INVALID, "a wrist camera on link %d is enabled already and fixed for the life of the handle", s->wrist_cam.link);
     }
+    if (s->stack_on) return fail(LCR_ERR_INVALID, "the observation stack is enabled already: enable the wrist camera first and the stack last");
     if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the wrist camera first and the planes second (they then cover it)");
     // the frames between two guard regions (include/lcr.h: LCR_WRIST_GUARD)
     const size_t bytes = (((size_t)s->dev.n * s->dev.img_h * s->dev.img_w * 3 + 255) & ~(size_t)255) + 2 * LCR_WRIST_GUARD;
@@ -1534,6 +1570,83 @@ int lcr_render_terminal_wrist(lcr_sim *s, const int32_t *env_ids_host, int count
         if (seg_host) HIPCHK(hipMemcpyAsync(seg_host + (size_t)done * px, base + o_s, px * c, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
     }
+    return LCR_OK;
+}
+
+// ---- the observation stack ----
+
+int lcr_obs_stack_check(const lcr_obs_stack_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (spec->frames < 1 || spec->frames > LCR_STACK_MAX_FRAMES) return fail(LCR_ERR_INVALID, "frames must lie in 1 .. %d, got %d", LCR_STACK_MAX_FRAMES, spec->frames);
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be a mask of 1 (front), 2 (top) and 4 (wrist), or 0 for every camera of the handle, got %u", spec->cameras);
+    if (spec->dtype != LCR_STACK_UINT8 && spec->dtype != LCR_STACK_FLOAT16 && spec->dtype != LCR_STACK_FLOAT32)
+        return fail(LCR_ERR_INVALID, "dtype must be 0 (uint8), 1 (float16) or 2 (float32), got %d", spec->dtype);
+    if (spec->reset_fill != LCR_STACK_FILL_REPEAT && spec->reset_fill != LCR_STACK_FILL_ZERO)
+        return fail(LCR_ERR_INVALID, "reset_fill must be 0 (repeat) or 1 (zero), got %d", spec->reset_fill);
+    return LCR_OK;
+}
+
+int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
+    // the argument first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_obs_stack_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to stack");
+    lcr_obs_stack_spec sp = *spec;
+    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the stack)");
+    if (s->stack_on) {
+        if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "an observation stack (frames %d, cameras %u, dtype %d, reset_fill %d) is enabled already and fixed for the life of the handle", s->stack_spec.frames,
+                    s->stack_spec.cameras, s->stack_spec.dtype, s->stack_spec.reset_fill);
+    }
+    LcrStack A{};
+    if (sp.cameras & LCR_STACK_CAM_FRONT) A.src[A.ncam++] = s->dev.img_front;
+    if (sp.cameras & LCR_STACK_CAM_TOP) A.src[A.ncam++] = s->dev.img_top;
+    if (sp.cameras & LCR_STACK_CAM_WRIST) A.src[A.ncam++] = s->wrist.img;
+    const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w, esize = sp.dtype == LCR_STACK_UINT8 ? 1 : sp.dtype == LCR_STACK_FLOAT16 ? 2 : 4;
+    const size_t per_env = (size_t)sp.frames * 3 * A.ncam * px * esize;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // guard, stack, guard (include/lcr.h: LCR_WRIST_GUARD), then the two snapshots of did_reset
+    size_t off = LCR_WRIST_GUARD + al(N * per_env) + LCR_WRIST_GUARD;
+    const size_t guarded = off;
+    size_t o_snap[2] = {off, off};
+    if (s->rstream) for (int p = 0; p < 2; p++) { o_snap[p] = off; off += al(N); }
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the observation stack failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    A.dst = base + LCR_WRIST_GUARD;
+    A.n = s->dev.n; A.pixels = (int)px; A.frames = sp.frames; A.dtype = sp.dtype;
+    A.zero_fill = sp.reset_fill == LCR_STACK_FILL_ZERO;
+    A.flags = nullptr; A.op = LCR_STACK_REFILL;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc && off > guarded) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    if (!rc) rc = lcr_launch_obs_stack(A, s->stream);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); return fail(LCR_ERR_UNSUPPORTED, "the observation stack of %d envs at %d x %d needs more workgroups than one launch takes", s->dev.n, s->dev.img_w, s->dev.img_h); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "filling the observation stack failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->stack = A;
+    s->stack_mem = mem;
+    s->stack_spec = sp;
+    s->stack_bytes_per_env = per_env;
+    for (int p = 0; p < 2; p++) s->snap_reset[p] = s->rstream ? (unsigned char *)(base + o_snap[p]) : nullptr;
+    s->stack_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_obs_stack(lcr_sim *s, lcr_obs_stack_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the stack is made behind the frames, on the second stream after a step: the handle's stream waits for it here)
+    memset(out, 0, sizeof *out);
+    if (!s->stack_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->stack_spec;
+    out->channels = 3 * s->stack.ncam;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->data = s->stack.dst;
+    out->bytes_per_env = (uint64_t)s->stack_bytes_per_env;
     return LCR_OK;
 }
 

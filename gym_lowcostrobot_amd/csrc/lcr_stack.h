@@ -1,0 +1,26 @@
+// lcr_stack.h -- the observation stack (lcr_enable_obs_stack, include/lcr.h): the arguments of its kernel and its launcher (lcr_stack.hip).
+// A header of its own: lcr_device.h and every kernel that knows nothing of the stack stay as they are.
+#ifndef LCR_STACK_H
+#define LCR_STACK_H
+#include <stddef.h>
+
+// what the kernel does with an env.  An env whose flag byte is set is always refilled; `op` is what happens to the others (and to all without flags).
+enum { LCR_STACK_PUSH = 0, LCR_STACK_NEWEST = 1, LCR_STACK_REFILL = 2 };
+
+#define LCR_STACK_TILE 1024   // pixels of one camera of one env a wave takes (the last tile of a frame may hold fewer, a multiple of 16)
+
+struct LcrStack {
+    const unsigned char *src[3];   // the selected cameras' frames in channel order, [n][pixels][3] each; src[i >= ncam] unused
+    void *dst;                     // [n][frames][3 ncam][pixels] of the element type
+    const unsigned char *flags;    // [n] or null
+    int n, ncam, pixels;           // pixels = img_h * img_w, a multiple of 16
+    int frames;                    // K, 1 .. 8
+    int dtype;                     // lcr_obs_stack_dtype
+    int op;                        // LCR_STACK_*
+    int zero_fill;                 // a refill writes zeros (not the new frames) to slots 0 .. K - 2
+};
+
+// 0, or the hipError_t of the launch; -1: arguments the kernel is not built for (nothing is launched)
+int lcr_launch_obs_stack(const LcrStack &A, void *stream);
+
+#endif

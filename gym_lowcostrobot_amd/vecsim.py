@@ -93,6 +93,7 @@ class VecSim:
         look_variants=None,
         look_sampler=None,
         wrist_camera=None,
+        obs_stack=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -130,6 +131,15 @@ class VecSim:
                 raise ValueError("wrist_camera needs image observations: observation_mode 'image' or 'both'")
             wrist_camera = _capi.WristCamera.from_any(wrist_camera)
             check(self.L.lcr_wrist_camera_check(ctypes.byref(wrist_camera)))
+        # the observation stack (lcr_enable_obs_stack): None = none, an int = that many frames of every camera as uint8, or a dict of frames / cameras / dtype / reset_fill.
+        # Checked here and by the library without a handle (lcr_obs_stack_check), before it is asked for a device
+        if obs_stack is not None:
+            if observation_mode == "state":
+                raise ValueError("obs_stack needs image observations: observation_mode 'image' or 'both'")
+            obs_stack = _capi.ObsStackSpec.from_any(obs_stack)
+            if obs_stack.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("obs_stack: cameras selects 'wrist', but no wrist_camera is given")
+            check(self.L.lcr_obs_stack_check(ctypes.byref(obs_stack)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -267,6 +277,17 @@ class VecSim:
                 check(self.L.lcr_get_wrist_camera(self.handle, ctypes.byref(wv)))
                 self.depth_wrist = DeviceArray(self, wv.depth_wrist, pl, np.float32) if wv.depth_wrist else None
                 self.seg_wrist = DeviceArray(self, wv.seg_wrist, pl, np.uint8) if wv.seg_wrist else None
+        self.obs_stack = self.obs_stack_spec = None
+        if obs_stack is not None:   # (last: behind look, wrist camera and planes)
+            try:
+                check(self.L.lcr_enable_obs_stack(self.handle, ctypes.byref(obs_stack)))
+                sv = _capi.LcrObsStackView()
+                check(self.L.lcr_get_obs_stack(self.handle, ctypes.byref(sv)))
+            except Exception:
+                self.close()
+                raise
+            self.obs_stack_spec = sv.spec.as_dict()
+            self.obs_stack = DeviceArray(self, sv.data, (N, int(sv.spec.frames), int(sv.channels)) + self.image_size, np.dtype(self.obs_stack_spec["dtype"]))
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -504,6 +525,8 @@ class VecSim:
                 obs["image_wrist"] = self.image_wrist.numpy()
             for k, a in self.plane_arrays().items():
                 obs[k] = a.numpy()
+            if self.obs_stack is not None:
+                obs["image_stack"] = self.obs_stack.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

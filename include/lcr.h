@@ -237,7 +237,7 @@ int lcr_nv(int task); /* 12, stack 18 */
 /* == EnvClass.__init__ (reach_cube_env.py:77-139): allocate device state for n_envs envs.  The envs are
  * left in the post-reset state of seed (base_seed + global env id). */
 int lcr_create(const lcr_config *cfg, lcr_sim **out);
-void lcr_destroy(lcr_sim *sim); /* == close() reach_cube_env.py:357-363 */
+void lcr_destroy(lcr_sim *sim); /* == close() reach_cube_env.py:357-363; frees everything the enable calls allocated (planes, look, wrist camera, observation stack) */
 
 /* Which step-kernel family this handle runs (decided at lcr_create from lcr_config.step_kernel and the shard size): 0 = one wave per 64 envs
  * (lcr_step_kernel), 1 / 2 = two cooperating waves per 64 envs (lcr_step2_kernel) compiled for one / two waves per SIMD. */
@@ -396,7 +396,8 @@ typedef struct lcr_look_sampler {      /* redraw an env's look whenever it is re
 /* Every colour lies in [0, 1] and every number is finite. */
 int lcr_look_variant_default(lcr_look_variant *v);   /* the values in the comments above */
 /* Switch the look on.  The arguments are checked before the handle is looked at (LCR_ERR_INVALID with the field's name in the message); then a NULL handle, a handle without
- * image observations, a moved camera less than 5 cm above the floor and a handle whose planes are already enabled (enable the look first, the planes second) are refused.
+ * image observations, a moved camera less than 5 cm above the floor, a handle whose planes are already enabled (enable the look first, the planes second) and one whose observation stack is on
+ * (lcr_enable_obs_stack comes last) are refused.
  * Builds the 2 n_variants cameras in fp64 (an all-zero offset gives the very floats of the scene cameras), ray-casts the n_variants cached background pairs, gives every env
  * variant 0 and its task's colours -- with a sampler the draw of episode 0 -- and redraws the frames.  Fixed for the life of the handle: a second call with the same
  * arguments does nothing, one with other arguments is refused. */
@@ -445,7 +446,7 @@ int lcr_wrist_camera_default(lcr_wrist_camera *cam);
 int lcr_wrist_camera_check(const lcr_wrist_camera *cam);
 /* Switch the wrist camera on.  `cam` is checked before the handle is looked at (LCR_ERR_INVALID with the field's name in the message: link outside 0 .. 6, pos out of
  * range, a zero X or a Y parallel to X -- norm after the projection < 1e-6 --, fovy_deg outside [20, 120], a number that is not finite); then a NULL handle, a handle without
- * image observations and a handle whose planes are already enabled are refused.  Allocates [N][H][W][3] and draws it from the current state; from then on whatever draws the
+ * image observations, a handle whose planes are already enabled and one whose observation stack is on (lcr_enable_obs_stack comes last) are refused.  Allocates [N][H][W][3] and draws it from the current state; from then on whatever draws the
  * two colour frames -- step, reset and its masked no-op form, lcr_set_look -- draws the wrist frames behind them, on the same stream, from the same pose snapshot.  Fixed for
  * the life of the handle: the same arguments again do nothing, other arguments are refused. */
 int lcr_enable_wrist_camera(lcr_sim *sim, const lcr_wrist_camera *cam);
@@ -456,6 +457,56 @@ int lcr_get_wrist_camera(lcr_sim *sim, lcr_wrist_view *out);
  * The batched last wrist frames of finished episodes: the sibling of lcr_render_terminal (same precondition, same terminal look), rgb_host [count][H][W][3]; depth_host /
  * seg_host [count][H][W] may be NULL, and must be where that plane is not enabled. */
 int lcr_render_terminal_wrist(lcr_sim *sim, const int32_t *env_ids_host, int count, uint8_t *rgb_host, float *depth_or_null, uint8_t *seg_or_null);
+
+/* == The observation stack: an optional device buffer per handle, [N][K][C][H][W] contiguous, that the library keeps current -- the cameras' frames channels-first, in the
+ * policy's element type, the last K of them per env.  Policy-ready as (N, K C, H, W) by a plain reshape: what SB3's VecTransposeImage + VecFrameStack or gymnasium's
+ * FrameStackObservation build on the host, here on the device, behind the frame kernels, with the one rule only the library can apply without a host round trip -- which envs
+ * the step has just auto-reset.  Off by default: without lcr_enable_obs_stack no byte, state, output or kernel of the handle changes.
+ *   channels  C = 3 x (number of selected cameras), in the order front, top, wrist, each as r, g, b.  `cameras` is a mask of LCR_STACK_CAM_* bits; 0 = every camera the handle
+ *             has.  The wrist bit on a handle without a wrist camera is refused.
+ *   slots     K = frames, 1 .. LCR_STACK_MAX_FRAMES.  Slot K - 1 is the newest, slot 0 the oldest.  K = 1 is the pure transpose and cast.
+ *   elements  of source byte x -- LCR_STACK_UINT8: x.  LCR_STACK_FLOAT32: (float)x * (1.0f / 255.0f), ONE correctly rounded float32 multiply by the float32 constant 1 / 255
+ *             (0x3b808081), not a division: bit for bit numpy's np.float32(x) * np.float32(1 / 255).  LCR_STACK_FLOAT16: that float32 value rounded to nearest even.
+ *   invariant after every entry point that draws frames, slot K - 1 of every env equals that env's current frames of the selected cameras.
+ *   lcr_step  (push) slots 1 .. K - 1 move to 0 .. K - 2 and the new frames go to slot K - 1.  An env with did_reset set in that step is instead REFILLED from its new
+ *             (reset-state) frames: LCR_STACK_FILL_REPEAT (default) writes them to all K slots (gymnasium's padding_type="reset"), LCR_STACK_FILL_ZERO writes zeros to
+ *             slots 0 .. K - 2 and the new frames to slot K - 1 (SB3's VecFrameStack).
+ *   lcr_reset masked envs are refilled (a NULL mask: all); unmasked envs have slot K - 1 rewritten and their older slots kept -- no time has passed for them.  This covers
+ *             the masked no-op form (an all-zero mask redraws after lcr_set_state).
+ *   lcr_set_look  slot K - 1 of every env is rewritten.      enabling: every env is refilled from its current frames.
+ *   ordering  the stack kernel runs behind the frame kernels, on whatever stream they ran on.  After an lcr_step with the second stream in use it reads a SNAPSHOT of did_reset
+ *             (N bytes beside the pose snapshots, two in turn): without it the step kernel of step k + 1 would overwrite the flags the stack of step k still has to read.
+ *             The event every other entry point waits for is recorded after the stack kernel: every entry point but the step sees a finished stack.
+ *   life      enabled last -- after look, wrist camera and planes -- and fixed for the life of the handle: the same arguments again do nothing, other arguments are refused,
+ *             and lcr_enable_look / lcr_enable_wrist_camera on a handle whose stack is on are refused.  The planes are not stacked; they may be enabled before or after.
+ *   guards    the stack lies between two regions of LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, [data - LCR_WRIST_GUARD, data) and LCR_WRIST_GUARD bytes from the first
+ *             256-byte boundary at or behind its end; filled once, never written afterwards.
+ *   not kept  the stack of an episode that ended: the refill overwrites the K - 1 older frames of a reset env, so there is no stacked terminal observation. */
+enum { LCR_STACK_CAM_FRONT = 1, LCR_STACK_CAM_TOP = 2, LCR_STACK_CAM_WRIST = 4 };
+typedef enum lcr_obs_stack_dtype { LCR_STACK_UINT8 = 0, LCR_STACK_FLOAT16 = 1, LCR_STACK_FLOAT32 = 2 } lcr_obs_stack_dtype;
+typedef enum lcr_obs_stack_fill { LCR_STACK_FILL_REPEAT = 0, LCR_STACK_FILL_ZERO = 1 } lcr_obs_stack_fill;
+#define LCR_STACK_MAX_FRAMES 8
+typedef struct lcr_obs_stack_spec {
+    int32_t frames;       /* K, 1 .. LCR_STACK_MAX_FRAMES */
+    uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+    int32_t dtype;        /* lcr_obs_stack_dtype */
+    int32_t reset_fill;   /* lcr_obs_stack_fill */
+} lcr_obs_stack_spec;
+typedef struct lcr_obs_stack_view {
+    int32_t enabled;                   /* 0: no stack, everything below is 0 / NULL */
+    lcr_obs_stack_spec spec;           /* as enabled, `cameras` resolved to the bits in use */
+    int32_t channels;                  /* C */
+    int32_t image_width, image_height;
+    const void *data;                  /* device, [N][K][C][H][W] of the element type */
+    uint64_t bytes_per_env;            /* K C H W sizeof(element) */
+} lcr_obs_stack_view;
+/* The checks lcr_enable_obs_stack makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field's name in the message */
+int lcr_obs_stack_check(const lcr_obs_stack_spec *spec);
+/* Switch the stack on.  `spec` is checked first; then a NULL handle, a handle without image observations and a wrist bit without a wrist camera are refused (LCR_ERR_INVALID);
+ * an allocation that fails is LCR_ERR_OOM.  Refills every env from its current frames. */
+int lcr_enable_obs_stack(lcr_sim *sim, const lcr_obs_stack_spec *spec);
+/* The stack; waits (on the handle's stream) for frames and stack still being made on the second stream, as every entry point but the step does. */
+int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
 
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
