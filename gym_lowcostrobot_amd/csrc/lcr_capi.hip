@@ -117,7 +117,8 @@ struct lcr_sim {
     char *host_mirror;
     // image observations: the frames of step k are ray-cast on a second stream from a snapshot of the poses while the step kernel of step k + 1 runs (lcr_step).  The
     // step kernel is VALU-bound and ends with a tail of few slow waves, the frame kernel is HBM-write-bound: together they take little more than the longer one.
-    // Every other entry point first makes the caller's stream wait for the pending frames (join_render), so nothing but lcr_step sees the second stream.
+    // Every entry point that takes the handle, except the four that touch no frame (lcr_step, lcr_fill_random_actions, lcr_get_outputs, lcr_step_kernel_family), first makes
+    // the caller's stream wait for the pending frames (join_render: a hipStreamWaitEvent, no host wait), so nothing but lcr_step sees the second stream.
     hipStream_t rstream;         // null: frames on the caller's stream, after the step kernel (LCR_RENDER_OVERLAP=0)
     hipEvent_t ev_snap[2], ev_rdone[2];
     float *snap_qpos[2], *snap_target[2];
@@ -632,7 +633,10 @@ int lcr_step_kernel_family(lcr_sim *s) {
 
 int lcr_set_stream(lcr_sim *s, void *hip_stream) {
     SIMCHK(s);
-    if (s->rstream) HIPCHK(hipStreamSynchronize(s->rstream));   // (nothing of the old stream's frames is in flight when the new stream takes over)
+    // nothing enqueued on the old stream -- a step kernel, a reset, lcr_fill_random_actions into a buffer the next step reads -- is in flight when the new stream takes over:
+    // the two streams are not ordered against each other otherwise.  (A host wait: the call is rare and never in a loop.)
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (s->rstream) HIPCHK(hipStreamSynchronize(s->rstream));   // (nor anything of the old stream's frames)
     s->stream = (hipStream_t)hip_stream;
     return LCR_OK;
 }
@@ -721,6 +725,7 @@ int lcr_step_host(lcr_sim *s, const float *action_host) {
 
 int lcr_get_obs(lcr_sim *s, lcr_obs_view *out) {
     if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (image_front / image_top are drawn on the second stream after a step: the handle's stream waits for them here)
     const size_t N = (size_t)s->dev.n;
     out->n_envs = s->dev.n;
     out->arm_qpos = s->dev.qpos;

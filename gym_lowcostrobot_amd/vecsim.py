@@ -42,6 +42,7 @@ class DeviceArray:
         return out
 
     def torch(self):
+        """zero-copy torch view; image views, planes, wrist frames and the stack are read on the handle's stream after VecSim.wait_frames() or any other joining call (lcr.h: lcr_step)"""
         import torch
 
         return torch.as_tensor(self, device=f"cuda:{self._sim.device}")
@@ -323,6 +324,11 @@ class VecSim:
 
     def sync(self):
         check(self.L.lcr_sync(self.handle))
+
+    def wait_frames(self):
+        """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
+        wrist frames, stack): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
     def reset(self, seeds=None, mask=None):

@@ -243,7 +243,9 @@ void lcr_destroy(lcr_sim *sim); /* == close() reach_cube_env.py:357-363; frees e
  * (lcr_step_kernel), 1 / 2 = two cooperating waves per 64 envs (lcr_step2_kernel) compiled for one / two waves per SIMD. */
 int lcr_step_kernel_family(lcr_sim *sim);
 
-/* HIP stream (hipStream_t passed as void*) all later work is enqueued on; NULL = default stream. */
+/* HIP stream (hipStream_t passed as void*) all later work is enqueued on; NULL = default stream.  Synchronises the OLD stream (a host wait, after making it wait for
+ * frames still being ray-cast) before it switches: whatever was enqueued on it -- a step, a reset, lcr_fill_random_actions -- has finished when work on the new stream
+ * begins, the two streams need no ordering of the caller's.  Meant to be called once, not in a loop. */
 int lcr_set_stream(lcr_sim *sim, void *hip_stream);
 int lcr_sync(lcr_sim *sim); /* hipStreamSynchronize on the handle's stream (after making it wait for frames still being ray-cast, see lcr_step) */
 
@@ -256,19 +258,24 @@ int lcr_reset(lcr_sim *sim, const uint8_t *mask_host, const uint64_t *seeds_host
 /* == step(action) (reach_cube_env.py:313-333) for all envs: apply_action (joint or ee+IK) -> 20 physics
  * substeps -> reward / terminated / truncated -> fused auto-reset.  action_dev: [k][N] float32.
  * Asynchronous.  With image observations the two frames of every env (at the configured size) are ray-cast on a second, internal stream from a snapshot of the poses, so that the step kernel of
- * the NEXT lcr_step overlaps them (BASELINE config 5: 9.7 -> see DESIGN.md section 3.4).  Every other entry point of this API first makes the handle's stream wait for
- * those frames; a caller that reads lcr_obs_view.image_* with its own kernels on the handle's stream calls lcr_sync (or any other entry point) first.
+ * the NEXT lcr_step overlaps them (BASELINE config 5: 9.7 -> see DESIGN.md section 3.4).  The planes, the wrist frames and the observation stack are made on the same
+ * stream, behind them.  Every other entry point that takes the handle first makes the handle's stream wait for all of these (a "join") -- EXCEPT lcr_step itself,
+ * lcr_fill_random_actions, lcr_get_outputs and lcr_step_kernel_family, which touch none of them; the calls that take no handle have no stream to join.  A join is a
+ * hipStreamWaitEvent on the handle's stream, not a host wait: the host goes on, and work enqueued on the handle's stream afterwards sees the frames of the last step.  A
+ * caller that reads lcr_obs_view.image_* (or the planes, the wrist frames, the stack) with its own kernels on the handle's stream calls a joining entry point after the
+ * step first: lcr_get_obs is the cheap one, lcr_sync also blocks the host.  Reads enqueued before the NEXT lcr_step are finished before that step's frames overwrite them.
  * LCR_RENDER_OVERLAP=0 in the environment: frames on the handle's stream, after the step kernel. */
 int lcr_step(lcr_sim *sim, const float *action_dev);
 /* Convenience for host callers (single-env facade): copies [k][N] host floats then steps. */
 int lcr_step_host(lcr_sim *sim, const float *action_host);
 
+/* Views into the state arrays and the two frames.  Joins (see lcr_step): what is enqueued on the handle's stream after this call reads the frames of the last step. */
 int lcr_get_obs(lcr_sim *sim, lcr_obs_view *out);
 /* == what DummyVecEnv.step_wait hands to SB3 (examples/gym_manipulation_sb3.py:34-39): state observations + rewards + flags of
  * all envs in ONE device-to-host copy into pinned memory (132 B/env), plus the terminal observations (72 B/env) only when some
  * env was reset.  Synchronises the handle's stream. */
 int lcr_fetch_host(lcr_sim *sim, lcr_host_view *out);
-int lcr_get_outputs(lcr_sim *sim, lcr_out_view *out);
+int lcr_get_outputs(lcr_sim *sim, lcr_out_view *out); /* does not join: the step kernel writes all of it, on the handle's stream */
 
 /* Full simulator state (replaces poking env.data.qpos / env.data.qvel, e.g. examples/dynamixel_gym_leader.py:96-98;
  * also checkpoint/resume and the "(qpos, qvel, action) triple" parity tests).  Host pointers, any may be
