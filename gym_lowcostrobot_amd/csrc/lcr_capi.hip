@@ -32,6 +32,30 @@ int fail(int code, const char *fmt, ...) {
         hipError_t _e = (expr);                                                                \
         if (_e != hipSuccess) return fail(LCR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
+// the status of a kernel launcher: 0, a hipError_t, or -- lcr_launch_obs_stack alone -- a negative number for arguments it refuses
+#define LAUNCHCHK(what, expr)                                                                  \
+    do {                                                                                       \
+        int _rc = (expr);                                                                      \
+        if (_rc) return fail(LCR_ERR_HIP, what " launch failed: %s", _rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)_rc)); \
+    } while (0)
+
+// grows the device scratch buffer `*buf` of `*have` bytes to `need` bytes (what it held is dropped)
+int reserve(void **buf, size_t *have, size_t need) {
+    if (need <= *have) return LCR_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    hipError_t e = hipMalloc(buf, need);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+    *have = need;
+    return LCR_OK;
+}
+
+// the layout of one allocation: slices handed out front to back, each rounded up to a multiple of 256 bytes
+struct Carver {
+    size_t off = 0;   // bytes handed out so far: the offset of the next slice, at the end the size of the allocation
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }   // (0 bytes: the offset of whatever follows, nothing taken)
+    size_t skip(size_t bytes) { const size_t o = off; off += bytes; return o; }                          // as it is, not rounded: the guard regions
+};
 }  // namespace
 
 namespace {
@@ -154,8 +178,6 @@ struct lcr_sim {
     unsigned char *snap_reset[2];      // beside snap_qpos / snap_target / snap_look
 };
 
-// whatever draws the handle's colour frames draws its enabled planes in the same launch
-// (`look`: the looks to draw P's envs with when they are not the current ones -- a snapshot)
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
 static LcrLook look_args(const lcr_sim *s, const LcrDev &P, const int *look) {
     LcrLook LK = s->look;
@@ -186,6 +208,14 @@ static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *fla
     return lcr_launch_obs_stack(A, stream);
 }
 
+// frames, then stack: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
+// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack)
+static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op) {
+    LAUNCHCHK("render", launch_frames(s, P, stream, look));
+    if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op));
+    return LCR_OK;
+}
+
 // the wrist camera's mount with the ray scale of a frame `height` rows high (s = 2 tan(fovy / 2) / height in fp64, then rounded)
 static LcrWristMount wrist_mount_at(const lcr_sim *s, int height) {
     LcrWristMount M = s->wrist.mount;
@@ -204,6 +234,60 @@ static int join_render(lcr_sim *s) {
         s->rpending = false;
     }
     return 0;
+}
+
+// ---- the staging and the pass loop of the three terminal-frame calls (lcr_render_terminal, lcr_render_terminal_planes, lcr_render_terminal_wrist) ----
+// one pass: `c` env ids to the device, their terminal poses gathered behind them and -- with a look -- their terminal looks.  P1: the c-env view of the handle over the
+// gathered poses (the caller points its frame buffers into the staging), LK: the looks to draw it with
+static int term_stage_gather(lcr_sim *s, const int32_t *ids_host, int c, char *base, size_t o_ids, size_t o_q, size_t o_t, size_t o_lk, LcrDev &P1, LcrLook &LK) {
+    HIPCHK(hipMemcpyAsync(base + o_ids, ids_host, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
+    LAUNCHCHK("gather", lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream));
+    P1 = s->dev;
+    P1.n = c;
+    P1.qpos = (float *)(base + o_q);
+    P1.target = (float *)(base + o_t);
+    LK = LcrLook{};
+    if (s->look_K) {
+        LAUNCHCHK("gather", lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream));
+        LK = look_args(s, P1, (const int *)(base + o_lk));
+    }
+    return LCR_OK;
+}
+
+// The driver of the three calls, behind their own argument checks.  `per_env`: the bytes per env of each buffer the caller's frame kernel writes (0: a buffer it does not
+// use).  The listed envs are drawn in passes of at most `cap` envs, as many as keep those buffers within the budget.  The staging -- the ids, the gathered poses, the
+// caller's buffers at `cap` envs each, the gathered looks -- is laid out once and used again by every pass, a shorter last pass filling the front of each slice.  In each
+// pass `pass(P1, LK, c, done, buf)` draws the `c` envs behind the first `done` ones: P1 and LK as term_stage_gather leaves them, buf[i] the device buffer of per_env[i]
+// (null where that is 0); it launches its frame kernel and enqueues the copies into its host arrays at env `done`; the driver waits for them.
+template <size_t NB, class Pass>
+static int render_terminal_passes(lcr_sim *s, const int32_t *env_ids_host, int count, const size_t (&per_env)[NB], Pass pass) {
+    for (int i = 0; i < count; i++)
+        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
+    size_t env_bytes = 0;
+    for (size_t b : per_env) env_bytes += b;
+    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass: 1 024 envs of two colour frames at 320 x 240 (2 x 225 KiB each), 19 200 at 64 x 64
+    const size_t chunk = BUDGET / env_bytes;
+    const int cap = (size_t)count < chunk ? count : (int)chunk;
+    if (cap == 0) return LCR_OK;
+    Carver C;
+    const size_t o_ids = C.take(sizeof(int) * cap);
+    const size_t o_q = C.take(sizeof(float) * s->nq * cap);
+    const size_t o_t = C.take(sizeof(float) * 3 * cap);
+    size_t o_buf[NB];
+    for (size_t i = 0; i < NB; i++) o_buf[i] = C.take(per_env[i] * cap);
+    const size_t o_lk = C.take(s->look_K ? sizeof(int) * 10 * cap : 0);   // the terminal looks of the listed envs
+    if (int rc = reserve(&s->term_stage, &s->term_stage_bytes, C.off)) return rc;
+    char *base = (char *)s->term_stage, *buf[NB];
+    for (size_t i = 0; i < NB; i++) buf[i] = per_env[i] ? base + o_buf[i] : nullptr;
+    for (int done = 0; done < count; done += cap) {
+        const int c = count - done < cap ? count - done : cap;
+        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
+        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
+        if (int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK)) return rc;
+        if (int rc = pass(P1, LK, c, (size_t)done, buf)) return rc;
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    return LCR_OK;
 }
 
 extern "C" {
@@ -375,51 +459,56 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     const size_t N = (size_t)cfg->n_envs;
 
     // ---- one arena for all SoA arrays (256-B aligned slices) ----
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    size_t o_qpos = off; off += al(sizeof(float) * s->nq * N);
-    size_t o_qvel = off; off += al(sizeof(float) * s->nv * N);
-    size_t o_ee = off; off += al(sizeof(float) * 3 * N);
-    size_t o_tgt = off; off += al(sizeof(float) * 3 * N);
+    Carver C;
+    const size_t o_qpos = C.take(sizeof(float) * s->nq * N);
+    const size_t o_qvel = C.take(sizeof(float) * s->nv * N);
+    const size_t o_ee = C.take(sizeof(float) * 3 * N);
+    const size_t o_tgt = C.take(sizeof(float) * 3 * N);
     // step outputs follow the observable state directly: [qpos .. did_reset] is ONE contiguous range, fetched by lcr_fetch_host
     // with a single device-to-host copy (the terminal observations behind it only when some env was reset)
-    size_t o_rew = off; off += al(sizeof(float) * N);
-    size_t o_term = off; off += al(N);
-    size_t o_trunc = off; off += al(N);
-    size_t o_succ = off; off += al(N);
-    size_t o_dres = off; off += al(N);
-    size_t o_fetch_end = off;
-    size_t o_tobs = off; off += al(sizeof(float) * LCR_OBS_DIM * N);
-    size_t o_tquat = off; off += al(sizeof(float) * 8 * N);
-    size_t o_tobs_end = off;
-    size_t o_el = off; off += al(sizeof(int) * N);
-    size_t o_rng = off; off += al(sizeof(unsigned long long) * 4 * N);
-    size_t o_goal = off; off += al(sizeof(int) * N);
-    size_t o_time = off; off += al(sizeof(double) * N);
-    size_t o_diag = off; if (cfg->diagnostics) off += 4 * al(sizeof(unsigned) * N) + al(sizeof(float) * 6 * N);
+    const size_t o_rew = C.take(sizeof(float) * N);
+    const size_t o_term = C.take(N);
+    const size_t o_trunc = C.take(N);
+    const size_t o_succ = C.take(N);
+    const size_t o_dres = C.take(N);
+    const size_t o_fetch_end = C.off;
+    const size_t o_tobs = C.take(sizeof(float) * LCR_OBS_DIM * N);
+    const size_t o_tquat = C.take(sizeof(float) * 8 * N);
+    const size_t o_tobs_end = C.off;
+    const size_t o_el = C.take(sizeof(int) * N);
+    const size_t o_rng = C.take(sizeof(unsigned long long) * 4 * N);
+    const size_t o_goal = C.take(sizeof(int) * N);
+    const size_t o_time = C.take(sizeof(double) * N);
+    const size_t diag_on = cfg->diagnostics ? 1 : 0;   // the diagnostics arrays take room only when they are asked for
+    const size_t o_dmask = C.take(diag_on * sizeof(unsigned) * N);
+    const size_t o_dcount = C.take(diag_on * sizeof(unsigned) * N);
+    const size_t o_dsweeps = C.take(diag_on * sizeof(unsigned) * N);
+    const size_t o_dchoice = C.take(diag_on * sizeof(unsigned) * N);
+    const size_t o_dctrl = C.take(diag_on * sizeof(float) * 6 * N);
     // scratch: Stack on the one-wave kernels keeps the g rows of the arm-link proxy slot (+ the rolling rows of the finger slots) here, 24 / 48 floats per env;
     // the two-wave kernels compiled for two waves per SIMD hand Wm = (M + hD)^-1 L from the cube wave to the arm wave through it in substeps with a finger on
     // a cube, 36 floats per lane of every (64-lane) workgroup
-    size_t o_scr = off; off += al(sizeof(float) * 48 * (((N + 63) / 64) * 64));
+    const size_t o_scr = C.take(sizeof(float) * 48 * (((N + 63) / 64) * 64));
     const bool carry_warm = !(cfg->compat & LCR_COMPAT_COLD_SOLVE_EACH_STEP);
-    size_t o_warm = off; if (carry_warm) off += al(sizeof(float) * LCR_NWARM * N);   // constraint forces carried between control steps
-    size_t o_act = off; off += al(sizeof(float) * 6 * N);
-    size_t o_mask = off; off += al(N);
-    size_t o_seeds = off; off += al(sizeof(unsigned long long) * N);
-    size_t o_img0 = off, o_img1 = off;
+    const size_t o_warm = C.take(carry_warm ? sizeof(float) * LCR_NWARM * N : 0);   // constraint forces carried between control steps
+    const size_t o_act = C.take(sizeof(float) * 6 * N);
+    const size_t o_mask = C.take(N);
+    const size_t o_seeds = C.take(sizeof(unsigned long long) * N);
     const int img_w = cfg->image_width ? cfg->image_width : LCR_IMG_W, img_h = cfg->image_height ? cfg->image_height : LCR_IMG_H;
     const size_t img_bytes = (size_t)img_h * img_w * 3;
-    size_t o_bg = off;
-    if (s->has_images) { o_img0 = off; off += al(img_bytes * N); o_img1 = off; off += al(img_bytes * N); o_bg = off; off += al(2 * img_bytes); }
+    const size_t o_img0 = C.take(s->has_images ? img_bytes * N : 0);
+    const size_t o_img1 = C.take(s->has_images ? img_bytes * N : 0);
+    const size_t o_bg = C.take(s->has_images ? 2 * img_bytes : 0);
+    const size_t off = C.off;
     s->arena_bytes = off;
     s->fetch_bytes = o_fetch_end;
     s->tobs_off = o_tobs;
     s->tobs_bytes = o_tobs_end - o_tobs;
     s->host_mirror = nullptr;
     e = hipMalloc(&s->arena, off);
-    if (e != hipSuccess) { delete s; return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) failed: %s", off, hipGetErrorString(e)); }
+    if (e != hipSuccess) { lcr_destroy(s); return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) failed: %s", off, hipGetErrorString(e)); }
     e = hipMemset(s->arena, 0, off);
-    if (e != hipSuccess) { (void)hipFree(s->arena); delete s; return fail(LCR_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { lcr_destroy(s); return fail(LCR_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(e)); }
     char *base = (char *)s->arena;
 
     LcrDev &D = s->dev;
@@ -543,11 +632,11 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     D.did_reset = (unsigned char *)(base + o_dres);
     D.term_obs = (float *)(base + o_tobs);
     D.term_quat = (float *)(base + o_tquat);
-    D.active_mask = cfg->diagnostics ? (unsigned *)(base + o_diag) : nullptr;
-    D.active_count = cfg->diagnostics ? (unsigned *)(base + o_diag + al(sizeof(unsigned) * N)) : nullptr;
-    D.max_sweeps = cfg->diagnostics ? (unsigned *)(base + o_diag + 2 * al(sizeof(unsigned) * N)) : nullptr;
-    D.choice = cfg->diagnostics ? (unsigned *)(base + o_diag + 3 * al(sizeof(unsigned) * N)) : nullptr;
-    D.ctrl_out = cfg->diagnostics ? (float *)(base + o_diag + 4 * al(sizeof(unsigned) * N)) : nullptr;
+    D.active_mask = cfg->diagnostics ? (unsigned *)(base + o_dmask) : nullptr;
+    D.active_count = cfg->diagnostics ? (unsigned *)(base + o_dcount) : nullptr;
+    D.max_sweeps = cfg->diagnostics ? (unsigned *)(base + o_dsweeps) : nullptr;
+    D.choice = cfg->diagnostics ? (unsigned *)(base + o_dchoice) : nullptr;
+    D.ctrl_out = cfg->diagnostics ? (float *)(base + o_dctrl) : nullptr;
     D.scratch = (float *)(base + o_scr);
     D.warm = carry_warm ? (float *)(base + o_warm) : nullptr;
     D.img_front = s->has_images ? (unsigned char *)(base + o_img0) : nullptr;
@@ -566,17 +655,17 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     s->seeds_dev = (unsigned long long *)(base + o_seeds);
     e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
-    if (e != hipSuccess) { (void)hipFree(s->arena); delete s; return fail(LCR_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { lcr_destroy(s); return fail(LCR_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e)); }
 
     // initial state: reset of seed (base_seed + global env id) for every env
     int rc = lcr_launch_reset(D, nullptr, nullptr, 1, cfg->base_seed, s->stream);
-    if (rc) { (void)hipFree(s->arena); delete s; return fail(LCR_ERR_HIP, "reset kernel launch failed: %s", hipGetErrorString((hipError_t)rc)); }
+    if (rc) { lcr_destroy(s); return fail(LCR_ERR_HIP, "reset kernel launch failed: %s", hipGetErrorString((hipError_t)rc)); }
     if (s->has_images) {
         lcr_launch_render_bg(D, s->cam_front, s->cam_top, s->stream);
         lcr_launch_render_obs(D, s->cam_front, s->cam_top, s->stream);
     }
     e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess) { (void)hipFree(s->arena); delete s; return fail(LCR_ERR_HIP, "initial reset failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { lcr_destroy(s); return fail(LCR_ERR_HIP, "initial reset failed: %s", hipGetErrorString(e)); }
     // the second stream of the frames (see lcr_sim); LCR_RENDER_OVERLAP=0: frames on the caller's stream, after the step kernel (A/B, profiling of one kernel at a time)
     const char *ro = getenv("LCR_RENDER_OVERLAP");
     if (s->has_images && !(ro && atoi(ro) == 0)) {
@@ -593,6 +682,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     return LCR_OK;
 }
 
+// (also what lcr_create unwinds a half-built handle through: whatever was never created is null and skipped)
 void lcr_destroy(lcr_sim *s) {
     if (!s) return;
     (void)hipSetDevice(s->cfg.device);
@@ -600,13 +690,14 @@ void lcr_destroy(lcr_sim *s) {
     if (s->rstream) {
         (void)hipStreamSynchronize(s->rstream);
         for (int p = 0; p < 2; p++) {
-            (void)hipEventDestroy(s->ev_snap[p]); (void)hipEventDestroy(s->ev_rdone[p]);
+            if (s->ev_snap[p]) (void)hipEventDestroy(s->ev_snap[p]);
+            if (s->ev_rdone[p]) (void)hipEventDestroy(s->ev_rdone[p]);
             (void)hipFree(s->snap_qpos[p]); (void)hipFree(s->snap_target[p]);
         }
         (void)hipStreamDestroy(s->rstream);
     }
-    (void)hipEventDestroy(s->ev0);
-    (void)hipEventDestroy(s->ev1);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->render_dev) (void)hipFree(s->render_dev);
     if (s->term_stage) (void)hipFree(s->term_stage);
     if (s->planes_mem) (void)hipFree(s->planes_mem);
@@ -652,20 +743,11 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
     const size_t N = (size_t)s->dev.n;
     if (mask_host) HIPCHK(hipMemcpyAsync(s->mask_dev, mask_host, N, hipMemcpyHostToDevice, s->stream));
     if (seeds_host) HIPCHK(hipMemcpyAsync(s->seeds_dev, seeds_host, N * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-    int rc = lcr_launch_reset(s->dev, mask_host ? s->mask_dev : nullptr, seeds_host ? s->seeds_dev : nullptr, 0, 0, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "reset kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (s->look_K) {   // the reset envs count an episode and -- with a sampler -- draw its look
-        rc = lcr_launch_look_redraw(s->dev.n, s->dev.env_off, mask_host ? s->mask_dev : nullptr, 0, s->look_sm, s->look_cur, s->look_episode, nullptr, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "look kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    if (s->has_images) {
-        rc = launch_frames(s, s->dev, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (s->stack_on) {   // masked envs (no mask: all) are refilled, the others have their newest slot rewritten
-            rc = launch_stack(s, s->stream, mask_host ? s->mask_dev : nullptr, mask_host ? LCR_STACK_NEWEST : LCR_STACK_REFILL);
-            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
-        }
-    }
+    LAUNCHCHK("reset kernel", lcr_launch_reset(s->dev, mask_host ? s->mask_dev : nullptr, seeds_host ? s->seeds_dev : nullptr, 0, 0, s->stream));
+    if (s->look_K)   // the reset envs count an episode and -- with a sampler -- draw its look
+        LAUNCHCHK("look kernel", lcr_launch_look_redraw(s->dev.n, s->dev.env_off, mask_host ? s->mask_dev : nullptr, 0, s->look_sm, s->look_cur, s->look_episode, nullptr, s->stream));
+    if (s->has_images)   // the stack: masked envs (no mask: all) are refilled, the others have their newest slot rewritten
+        if (int rc = frames_after(s, s->dev, s->stream, nullptr, mask_host ? s->mask_dev : nullptr, mask_host ? LCR_STACK_NEWEST : LCR_STACK_REFILL)) return rc;
     // the staging copies above read caller memory: do not return before they are consumed
     if (mask_host || seeds_host) HIPCHK(hipStreamSynchronize(s->stream));
     return LCR_OK;
@@ -674,12 +756,9 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
 int lcr_step(lcr_sim *s, const float *action_dev) {
     SIMCHK_NOJOIN(s);
     if (!action_dev) return fail(LCR_ERR_INVALID, "action is NULL");
-    int rc = lcr_launch_step(s->dev, action_dev, s->ee_mode, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "step kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (s->look_K) {   // envs the step has auto-reset: their look becomes the terminal look, they count an episode and draw its look -- before the snapshot below
-        rc = lcr_launch_look_redraw(s->dev.n, s->dev.env_off, s->dev.did_reset, 0, s->look_sm, s->look_cur, s->look_episode, s->look_term, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "look kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
+    LAUNCHCHK("step kernel", lcr_launch_step(s->dev, action_dev, s->ee_mode, s->stream));
+    if (s->look_K)   // envs the step has auto-reset: their look becomes the terminal look, they count an episode and draw its look -- before the snapshot below
+        LAUNCHCHK("look kernel", lcr_launch_look_redraw(s->dev.n, s->dev.env_off, s->dev.did_reset, 0, s->look_sm, s->look_cur, s->look_episode, s->look_term, s->stream));
     if (s->has_images && s->rstream) {
         // the frame kernel reads qpos and target only: snapshot them (2.7 MB for 32 768 StackTwoCubes envs against 15 GB of frames), then ray-cast on the second stream while
         // this stream goes on with the next step.  Two snapshots in turn; the one about to be overwritten was read by the frames of two steps ago.
@@ -696,21 +775,12 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         HIPCHK(hipStreamWaitEvent(s->rstream, s->ev_snap[p], 0));
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
-        rc = launch_frames(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (s->stack_on) {   // before ev_rdone: join_render then covers the stack as it covers the frames
-            rc = launch_stack(s, s->rstream, s->snap_reset[p], LCR_STACK_PUSH);
-            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
-        }
+        // (the stack before ev_rdone: join_render then covers it as it covers the frames)
+        if (int rc = frames_after(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr, s->snap_reset[p], LCR_STACK_PUSH)) return rc;
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
-    } else if (s->has_images) {
-        rc = launch_frames(s, s->dev, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (s->stack_on) {   // same stream as the step kernel: did_reset itself is current until the next step
-            rc = launch_stack(s, s->stream, s->dev.did_reset, LCR_STACK_PUSH);
-            if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
-        }
+    } else if (s->has_images) {   // same stream as the step kernel: did_reset itself is current until the next step
+        if (int rc = frames_after(s, s->dev, s->stream, nullptr, s->dev.did_reset, LCR_STACK_PUSH)) return rc;
     }
     return LCR_OK;
 }
@@ -893,8 +963,7 @@ int lcr_timer_end(lcr_sim *s, float *ms_out) {
 int lcr_fill_random_actions(lcr_sim *s, float *action_dev, uint64_t seed, uint64_t step) {
     SIMCHK_NOJOIN(s);   // (writes the caller's action buffer only)
     if (!action_dev) return fail(LCR_ERR_INVALID, "action is NULL");
-    int rc = lcr_launch_fill_actions(action_dev, s->dev.n, s->k, s->dev.env_off, seed, step, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "fill kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    LAUNCHCHK("fill kernel", lcr_launch_fill_actions(action_dev, s->dev.n, s->k, s->dev.env_off, seed, step, s->stream));
     return LCR_OK;
 }
 
@@ -906,147 +975,101 @@ static int look_variant_of(lcr_sim *s, int env, int *v) {
     return LCR_OK;
 }
 
+// ---- the four single-frame calls (lcr_render, lcr_render_state, lcr_render_planes, lcr_render_state_planes) ----
+// Each checks its own arguments, then FRAMECHK; lays the scratch frame out (a Carver over render_dev: the frame or the two planes, for a caller's pose stage_pose behind
+// them); and ends in one of two tails, render_colour_of or render_planes_of, which resolve the camera (single_cam), launch and copy out.
+
+// the camera and the frame size a single-frame call accepts
+#define FRAMECHK(s, camera, width, height)                                                                                                       \
+    do {                                                                                                                                         \
+        CAMCHK(s, camera);                                                                                                                       \
+        if ((width) <= 0 || (height) <= 0 || (size_t)(width) * (height) > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size"); \
+    } while (0)
+
+// scene camera `camera` with the ray scale of a frame `height` rows high.  `look_env` >= 0 on a handle with a look: that env's own view, i.e. through its variant's camera
+// when `camera` is an observation camera (camera_vizu stays where it is)
+static int single_cam(lcr_sim *s, int camera, int height, int look_env, LcrCam &cam) {
+    cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
+    cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
+    if (look_env >= 0 && s->look_K && camera < 2) {
+        int v = 0;
+        if (int lr = look_variant_of(s, look_env, &v)) return lr;
+        make_look_camera(s->look_variants[v], camera, height, cam);
+    }
+    return LCR_OK;
+}
+
+// grows the scratch frame to what `C` has laid out plus a pose and stages the caller's pose there.  P1: a one-env view of the handle whose state arrays are that pose
+static int stage_pose(lcr_sim *s, Carver &C, const double *qpos_host, const float *target_host, LcrDev &P1) {
+    float st[32];
+    const size_t o_pose = C.take(sizeof st);
+    if (int rc = reserve((void **)&s->render_dev, &s->render_bytes, C.off)) return rc;
+    for (int i = 0; i < s->nq; i++) st[i] = (float)qpos_host[i];
+    for (int i = 0; i < 3; i++) st[s->nq + i] = target_host ? target_host[i] : 0.f;
+    float *stage = (float *)(s->render_dev + o_pose);
+    HIPCHK(hipMemcpyAsync(stage, st, sizeof(float) * (s->nq + 3), hipMemcpyHostToDevice, s->stream));
+    P1 = s->dev;
+    P1.n = 1;
+    P1.qpos = stage;
+    P1.target = stage + s->nq;
+    return LCR_OK;
+}
+
+// one colour frame of the pose arrays of `P` (env `env`), drawn at the start of the scratch frame and copied to the host (`look_env` >= 0: with that env's look)
+static int render_colour_of(lcr_sim *s, const LcrDev &P, int env, int camera, int width, int height, uint8_t *rgb_host, int look_env = -1) {
+    const bool look = look_env >= 0 && s->look_K;
+    if (camera == 3)   // the wrist camera of the pose
+        LAUNCHCHK("render", lcr_launch_render_single_wrist(P, wrist_mount_at(s, height), env, width, height, 0.f, s->render_dev, nullptr, nullptr, look ? &s->look : nullptr, look_env, P.n, s->stream));
+    else {
+        LcrCam cam;
+        if (int rc = single_cam(s, camera, height, look_env, cam)) return rc;
+        // (a look: the variant's colours and light, the env's colours)
+        if (look) LAUNCHCHK("render", lcr_launch_render_single_look(P, cam, env, width, height, s->render_dev, s->look, look_env, P.n, s->stream));
+        else LAUNCHCHK("render", lcr_launch_render_single(P, cam, env, width, height, s->render_dev, s->stream));
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(rgb_host, s->render_dev, (size_t)width * height * 3, hipMemcpyDeviceToHost));
+    return LCR_OK;
+}
+
 int lcr_render(lcr_sim *s, int env, int camera, int width, int height, uint8_t *rgb_host) {
     SIMCHK(s);
     if (!rgb_host) return fail(LCR_ERR_INVALID, "rgb_host is NULL");
     if (env < 0 || env >= s->dev.n) return fail(LCR_ERR_INVALID, "env %d out of range", env);
-    CAMCHK(s, camera);
-    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
-    LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
-    cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
-    const size_t bytes = (size_t)width * height * 3;
-    if (bytes > s->render_bytes) {
-        if (s->render_dev) (void)hipFree(s->render_dev);
-        s->render_dev = nullptr; s->render_bytes = 0;
-        hipError_t e = hipMalloc((void **)&s->render_dev, bytes);
-        if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        s->render_bytes = bytes;
-    }
-    int rc;
-    if (camera == 3)   // the wrist camera of env's pose, with env's look where the handle has one
-        rc = lcr_launch_render_single_wrist(s->dev, wrist_mount_at(s, height), env, width, height, 0.f, s->render_dev, nullptr, nullptr, s->look_K ? &s->look : nullptr, env, s->dev.n, s->stream);
-    else if (s->look_K) {   // env's own look: cameras 0 and 1 are its variant's, camera_vizu stays where it is; the variant's colours and light, the env's colours
-        if (camera < 2) {
-            int v = 0;
-            if (int lr = look_variant_of(s, env, &v)) return lr;
-            make_look_camera(s->look_variants[v], camera, height, cam);
-        }
-        rc = lcr_launch_render_single_look(s->dev, cam, env, width, height, s->render_dev, s->look, env, s->dev.n, s->stream);
-    } else rc = lcr_launch_render_single(s->dev, cam, env, width, height, s->render_dev, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(rgb_host, s->render_dev, bytes, hipMemcpyDeviceToHost));
-    return LCR_OK;
+    FRAMECHK(s, camera, width, height);
+    if (int rc = reserve((void **)&s->render_dev, &s->render_bytes, (size_t)width * height * 3)) return rc;   // (the frame alone: nothing is staged behind it)
+    return render_colour_of(s, s->dev, env, camera, width, height, rgb_host, env);
 }
 
 int lcr_render_state(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, uint8_t *rgb_host) {
     SIMCHK(s);
     if (!rgb_host || !qpos_host) return fail(LCR_ERR_INVALID, "NULL argument");
-    CAMCHK(s, camera);
-    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
-    LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
-    cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
-    const size_t bytes = (size_t)width * height * 3, frame = (bytes + 255) & ~(size_t)255, need = frame + 256;
-    if (need > s->render_bytes) {
-        if (s->render_dev) (void)hipFree(s->render_dev);
-        s->render_dev = nullptr; s->render_bytes = 0;
-        hipError_t e = hipMalloc((void **)&s->render_dev, need);
-        if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        s->render_bytes = need;
-    }
-    // a one-env view of the handle whose state arrays are the caller's pose, staged behind the frame
-    float st[32];
-    for (int i = 0; i < s->nq; i++) st[i] = (float)qpos_host[i];
-    for (int i = 0; i < 3; i++) st[s->nq + i] = target_host ? target_host[i] : 0.f;
-    float *stage = (float *)(s->render_dev + frame);
-    HIPCHK(hipMemcpyAsync(stage, st, sizeof(float) * (s->nq + 3), hipMemcpyHostToDevice, s->stream));
-    LcrDev P1 = s->dev;
-    P1.n = 1;
-    P1.qpos = stage;
-    P1.target = stage + s->nq;
-    int rc = camera == 3 ? lcr_launch_render_single_wrist(P1, wrist_mount_at(s, height), 0, width, height, 0.f, s->render_dev, nullptr, nullptr, nullptr, -1, 1, s->stream)
-                         : lcr_launch_render_single(P1, cam, 0, width, height, s->render_dev, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(rgb_host, s->render_dev, bytes, hipMemcpyDeviceToHost));
-    return LCR_OK;
-}
-
-// ---- the staging of the three terminal-frame calls (lcr_render_terminal, lcr_render_terminal_planes, lcr_render_terminal_wrist) ----
-// grows the staging buffer to `need` bytes
-static int term_stage_reserve(lcr_sim *s, size_t need) {
-    if (need <= s->term_stage_bytes) return LCR_OK;
-    if (s->term_stage) (void)hipFree(s->term_stage);
-    s->term_stage = nullptr; s->term_stage_bytes = 0;
-    hipError_t e = hipMalloc(&s->term_stage, need);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-    s->term_stage_bytes = need;
-    return LCR_OK;
-}
-// one pass: `c` env ids to the device, their terminal poses gathered behind them and -- with a look -- their terminal looks.  P1: the c-env view of the handle over the
-// gathered poses (the caller points its frame buffers into the staging), LK: the looks to draw it with
-static int term_stage_gather(lcr_sim *s, const int32_t *ids_host, int c, char *base, size_t o_ids, size_t o_q, size_t o_t, size_t o_lk, LcrDev &P1, LcrLook &LK) {
-    HIPCHK(hipMemcpyAsync(base + o_ids, ids_host, sizeof(int) * c, hipMemcpyHostToDevice, s->stream));
-    int rc = lcr_launch_gather_terminal(s->dev, (const int *)(base + o_ids), c, (float *)(base + o_q), (float *)(base + o_t), s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-    P1 = s->dev;
-    P1.n = c;
-    P1.qpos = (float *)(base + o_q);
-    P1.target = (float *)(base + o_t);
-    LK = LcrLook{};
-    if (s->look_K) {
-        rc = lcr_launch_look_gather((const int *)(base + o_ids), c, s->dev.n, s->look_term, (int *)(base + o_lk), s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "gather launch failed: %s", hipGetErrorString((hipError_t)rc));
-        LK = look_args(s, P1, (const int *)(base + o_lk));
-    }
-    return LCR_OK;
+    FRAMECHK(s, camera, width, height);
+    Carver C;
+    C.take((size_t)width * height * 3);
+    LcrDev P1;
+    if (int rc = stage_pose(s, C, qpos_host, target_host, P1)) return rc;
+    return render_colour_of(s, P1, 0, camera, width, height, rgb_host);
 }
 
 int lcr_render_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, uint8_t *front_host, uint8_t *top_host) {
     SIMCHK(s);
     if (count < 0 || (count > 0 && (!env_ids_host || !front_host || !top_host))) return fail(LCR_ERR_INVALID, "NULL argument");
     if (!s->has_images) return fail(LCR_ERR_UNSUPPORTED, "terminal frames need observation_mode image / both (the frame background is only kept then)");
-    for (int i = 0; i < count; i++)
-        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
     const size_t img = (size_t)s->dev.img_h * s->dev.img_w * 3;
-    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass: 1 024 envs at 320 x 240 (2 x 225 KiB each), 19 200 at 64 x 64
-    const size_t chunk = BUDGET / (2 * img);
-    const int cap = (size_t)count < chunk ? count : (int)chunk;
-    if (cap == 0) return LCR_OK;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_ids = 0, o_q = al(sizeof(int) * cap), o_t = o_q + al(sizeof(float) * s->nq * cap), o_f = o_t + al(sizeof(float) * 3 * cap),
-                 o_tp = o_f + al(img * cap), o_lk = o_tp + al(img * cap), need = o_lk + (s->look_K ? al(sizeof(int) * 10 * cap) : 0);   // (o_lk: the terminal looks of the listed envs)
-    if (int rc = term_stage_reserve(s, need)) return rc;
-    char *base = (char *)s->term_stage;
-    for (int done = 0; done < count; done += cap) {
-        const int c = count - done < cap ? count - done : cap;
-        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
-        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
-        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
-        if (rc) return rc;
-        P1.img_front = (unsigned char *)(base + o_f);
-        P1.img_top = (unsigned char *)(base + o_tp);
-        if (s->look_K) rc = lcr_launch_render_obs_look(P1, LK, nullptr, s->stream);
-        else rc = lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-        HIPCHK(hipMemcpyAsync(front_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipMemcpyAsync(top_host + (size_t)done * img, base + o_tp, img * c, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    return LCR_OK;
+    const size_t per_env[] = {img, img};   // front, top
+    return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
+        P1.img_front = (unsigned char *)buf[0];
+        P1.img_top = (unsigned char *)buf[1];
+        if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, nullptr, s->stream));
+        else LAUNCHCHK("render", lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream));
+        HIPCHK(hipMemcpyAsync(front_host + done * img, buf[0], img * c, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(top_host + done * img, buf[1], img * c, hipMemcpyDeviceToHost, s->stream));
+        return LCR_OK;
+    });
 }
 
 // ---- depth / segmentation planes of the image observations ----
-
-static int ensure_render_scratch(lcr_sim *s, size_t need) {
-    if (need <= s->render_bytes) return LCR_OK;
-    if (s->render_dev) (void)hipFree(s->render_dev);
-    s->render_dev = nullptr; s->render_bytes = 0;
-    hipError_t e = hipMalloc((void **)&s->render_dev, need);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-    s->render_bytes = need;
-    return LCR_OK;
-}
 
 int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
@@ -1064,20 +1087,23 @@ int lcr_enable_image_planes(lcr_sim *s, uint32_t planes, float depth_far) {
                     (double)s->pl.far, planes, (double)depth_far);
     }
     const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const bool dep = planes & LCR_PLANE_DEPTH, seg = planes & LCR_PLANE_SEGMENTATION;
     const size_t nbg = s->look_K ? (size_t)s->look_K : 1;   // with a look: the background planes of every variant's cameras, [K][2][H][W]
-    size_t off = 0;
-    const size_t o_bgd = off; off += al(nbg * 2 * px * sizeof(float));
-    const size_t o_bgs = off; off += al(nbg * 2 * px);
-    const size_t o_d0 = off; if (dep) off += al(N * px * sizeof(float));
-    const size_t o_d1 = off; if (dep) off += al(N * px * sizeof(float));
-    const size_t o_s0 = off; if (seg) off += al(N * px);
-    const size_t o_s1 = off; if (seg) off += al(N * px);
+    const size_t dbytes = dep ? N * px * sizeof(float) : 0, sbytes = seg ? N * px : 0;   // one camera's planes (0: not enabled, no room taken)
+    Carver C;
+    const size_t o_bgd = C.take(nbg * 2 * px * sizeof(float));
+    const size_t o_bgs = C.take(nbg * 2 * px);
+    const size_t o_d0 = C.take(dbytes);
+    const size_t o_d1 = C.take(dbytes);
+    const size_t o_s0 = C.take(sbytes);
+    const size_t o_s1 = C.take(sbytes);
     // the planes cover the wrist camera; LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE before, between and behind them (include/lcr.h)
-    const size_t o_g2 = off; if (s->wrist_on) off += LCR_WRIST_GUARD;
-    const size_t o_d2 = off; if (dep && s->wrist_on) off += al(N * px * sizeof(float)) + LCR_WRIST_GUARD;
-    const size_t o_s2 = off; if (seg && s->wrist_on) off += al(N * px) + LCR_WRIST_GUARD;
+    const size_t o_g2 = C.skip(s->wrist_on ? LCR_WRIST_GUARD : 0);
+    const size_t o_d2 = C.take(s->wrist_on ? dbytes : 0);
+    if (dep && s->wrist_on) C.skip(LCR_WRIST_GUARD);
+    const size_t o_s2 = C.take(s->wrist_on ? sbytes : 0);
+    if (seg && s->wrist_on) C.skip(LCR_WRIST_GUARD);
+    const size_t off = C.off;
     void *mem = nullptr;
     hipError_t e = hipMalloc(&mem, off);
     if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the image planes failed: %s", off, hipGetErrorString(e));
@@ -1132,23 +1158,17 @@ int lcr_get_image_planes(lcr_sim *s, lcr_planes_view *out) {
     return LCR_OK;
 }
 
-// one frame's planes of the pose arrays of `P` (env `env`), drawn into the scratch frame and copied to the host
+// one frame's planes of the pose arrays of `P` (env `env`), drawn into the scratch frame -- depth at its start, segmentation at `o_seg` -- and copied to the host
 // (`look_env` >= 0: with that env's look, i.e. through its variant's camera when `camera` is an observation camera -- colours and light do not show in the planes)
 static int render_planes_of(lcr_sim *s, const LcrDev &P, int env, int camera, int width, int height, size_t o_seg, float *depth_host, uint8_t *seg_host, int look_env = -1) {
-    LcrCam cam = camera == 0 ? s->cam_front : (camera == 1 ? s->cam_top : s->cam_vizu);
-    cam.s = (float)(2.0 * std::tan(0.5 * 45.0 * M_PI / 180.0) / height);
-    if (look_env >= 0 && s->look_K && camera < 2) {
-        int v = 0;
-        if (int lr = look_variant_of(s, look_env, &v)) return lr;
-        make_look_camera(s->look_variants[v], camera, height, cam);
-    }
+    LcrCam cam;
+    if (int rc = single_cam(s, camera, height, look_env, cam)) return rc;
     const size_t px = (size_t)width * height;
     const float far = s->planes ? s->pl.far : 10.f;
     float *depth_dev = depth_host ? (float *)s->render_dev : nullptr;
     unsigned char *seg_dev = seg_host ? s->render_dev + o_seg : nullptr;
-    int rc = camera == 3 ? lcr_launch_render_single_wrist(P, wrist_mount_at(s, height), env, width, height, far, nullptr, depth_dev, seg_dev, nullptr, -1, 1, s->stream)
-                         : lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_dev, seg_dev, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (camera == 3) LAUNCHCHK("render", lcr_launch_render_single_wrist(P, wrist_mount_at(s, height), env, width, height, far, nullptr, depth_dev, seg_dev, nullptr, -1, 1, s->stream));
+    else LAUNCHCHK("render", lcr_launch_render_single_planes(P, cam, env, width, height, far, depth_dev, seg_dev, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (depth_host) HIPCHK(hipMemcpy(depth_host, s->render_dev, px * sizeof(float), hipMemcpyDeviceToHost));
     if (seg_host) HIPCHK(hipMemcpy(seg_host, s->render_dev + o_seg, px, hipMemcpyDeviceToHost));
@@ -1159,30 +1179,23 @@ int lcr_render_planes(lcr_sim *s, int env, int camera, int width, int height, fl
     SIMCHK(s);
     if (!depth_host && !seg_host) return fail(LCR_ERR_INVALID, "depth_host and seg_host are both NULL");
     if (env < 0 || env >= s->dev.n) return fail(LCR_ERR_INVALID, "env %d out of range", env);
-    CAMCHK(s, camera);
-    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
-    const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255;
-    if (int rc = ensure_render_scratch(s, o_seg + px)) return rc;
+    FRAMECHK(s, camera, width, height);
+    Carver C;
+    C.take((size_t)width * height * sizeof(float));
+    const size_t o_seg = C.off;
+    if (int rc = reserve((void **)&s->render_dev, &s->render_bytes, o_seg + (size_t)width * height)) return rc;   // (the last slice as long as it is: nothing is staged behind it)
     return render_planes_of(s, s->dev, env, camera, width, height, o_seg, depth_host, seg_host, env);
 }
 
 int lcr_render_state_planes(lcr_sim *s, int camera, int width, int height, const double *qpos_host, const float *target_host, float *depth_host, uint8_t *seg_host) {
     SIMCHK(s);
     if (!qpos_host || (!depth_host && !seg_host)) return fail(LCR_ERR_INVALID, "NULL argument");
-    CAMCHK(s, camera);
-    if (width <= 0 || height <= 0 || (size_t)width * height > ((size_t)1 << 26)) return fail(LCR_ERR_INVALID, "bad frame size");
-    const size_t px = (size_t)width * height, o_seg = (px * sizeof(float) + 255) & ~(size_t)255, o_pose = (o_seg + px + 255) & ~(size_t)255;
-    if (int rc = ensure_render_scratch(s, o_pose + 256)) return rc;
-    // a one-env view of the handle whose state arrays are the caller's pose, staged behind the planes
-    float st[32];
-    for (int i = 0; i < s->nq; i++) st[i] = (float)qpos_host[i];
-    for (int i = 0; i < 3; i++) st[s->nq + i] = target_host ? target_host[i] : 0.f;
-    float *stage = (float *)(s->render_dev + o_pose);
-    HIPCHK(hipMemcpyAsync(stage, st, sizeof(float) * (s->nq + 3), hipMemcpyHostToDevice, s->stream));
-    LcrDev P1 = s->dev;
-    P1.n = 1;
-    P1.qpos = stage;
-    P1.target = stage + s->nq;
+    FRAMECHK(s, camera, width, height);
+    Carver C;
+    C.take((size_t)width * height * sizeof(float));
+    const size_t o_seg = C.take((size_t)width * height);
+    LcrDev P1;
+    if (int rc = stage_pose(s, C, qpos_host, target_host, P1)) return rc;
     return render_planes_of(s, P1, 0, camera, width, height, o_seg, depth_host, seg_host);
 }
 
@@ -1192,55 +1205,29 @@ int lcr_render_terminal_planes(lcr_sim *s, const int32_t *env_ids_host, int coun
     const bool dep = s->planes & LCR_PLANE_DEPTH, seg = s->planes & LCR_PLANE_SEGMENTATION;
     if (count < 0 || (count > 0 && (!env_ids_host || (dep && (!depth_front || !depth_top)) || (seg && (!seg_front || !seg_top)))))
         return fail(LCR_ERR_INVALID, "NULL argument (only the pointers of a plane that is not enabled may be NULL)");
-    for (int i = 0; i < count; i++)
-        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
     // the frame kernel draws the colours in the same launch: they are staged too and dropped
-    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, per_env = 2 * (img + (dep ? px * sizeof(float) : 0) + (seg ? px : 0));
-    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass, as lcr_render_terminal
-    const size_t chunk = BUDGET / per_env;
-    const int cap = (size_t)count < chunk ? count : (int)chunk;
-    if (cap == 0) return LCR_OK;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    const size_t o_ids = off; off += al(sizeof(int) * cap);
-    const size_t o_q = off; off += al(sizeof(float) * s->nq * cap);
-    const size_t o_t = off; off += al(sizeof(float) * 3 * cap);
-    const size_t o_f = off; off += al(img * cap);
-    const size_t o_tp = off; off += al(img * cap);
-    const size_t o_d0 = off; if (dep) off += al(px * sizeof(float) * cap);
-    const size_t o_d1 = off; if (dep) off += al(px * sizeof(float) * cap);
-    const size_t o_s0 = off; if (seg) off += al(px * cap);
-    const size_t o_s1 = off; if (seg) off += al(px * cap);
-    const size_t o_lk = off; if (s->look_K) off += al(sizeof(int) * 10 * cap);   // the terminal looks of the listed envs
-    if (int rc = term_stage_reserve(s, off)) return rc;
-    char *base = (char *)s->term_stage;
-    for (int done = 0; done < count; done += cap) {
-        const int c = count - done < cap ? count - done : cap;
-        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
-        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
-        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
-        if (rc) return rc;
-        P1.img_front = (unsigned char *)(base + o_f);
-        P1.img_top = (unsigned char *)(base + o_tp);
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, dpx = dep ? px * sizeof(float) : 0, spx = seg ? px : 0;
+    const size_t per_env[] = {img, img, dpx, dpx, spx, spx};   // front, top of the colours, the depths, the segmentations
+    return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
+        P1.img_front = (unsigned char *)buf[0];
+        P1.img_top = (unsigned char *)buf[1];
         LcrPlanes PL1 = s->pl;
-        PL1.depth_front = dep ? (float *)(base + o_d0) : nullptr;
-        PL1.depth_top = dep ? (float *)(base + o_d1) : nullptr;
-        PL1.seg_front = seg ? (unsigned char *)(base + o_s0) : nullptr;
-        PL1.seg_top = seg ? (unsigned char *)(base + o_s1) : nullptr;
-        if (s->look_K) rc = lcr_launch_render_obs_look(P1, LK, &PL1, s->stream);
-        else rc = lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
+        PL1.depth_front = (float *)buf[2];
+        PL1.depth_top = (float *)buf[3];
+        PL1.seg_front = (unsigned char *)buf[4];
+        PL1.seg_top = (unsigned char *)buf[5];
+        if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, &PL1, s->stream));
+        else LAUNCHCHK("render", lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream));
         if (dep) {
-            HIPCHK(hipMemcpyAsync(depth_front + (size_t)done * px, base + o_d0, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipMemcpyAsync(depth_top + (size_t)done * px, base + o_d1, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(depth_front + done * px, buf[2], dpx * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(depth_top + done * px, buf[3], dpx * c, hipMemcpyDeviceToHost, s->stream));
         }
         if (seg) {
-            HIPCHK(hipMemcpyAsync(seg_front + (size_t)done * px, base + o_s0, px * c, hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipMemcpyAsync(seg_top + (size_t)done * px, base + o_s1, px * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(seg_front + done * px, buf[4], spx * c, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(seg_top + done * px, buf[5], spx * c, hipMemcpyDeviceToHost, s->stream));
         }
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    return LCR_OK;
+        return LCR_OK;
+    });
 }
 
 // ---- the look of the image observations ----
@@ -1320,15 +1307,15 @@ int lcr_enable_look(lcr_sim *s, int n_variants, const lcr_look_variant *variants
     if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the look first and the planes second (their cached backgrounds are drawn per variant)");
 
     const size_t N = (size_t)s->dev.n, img = (size_t)s->dev.img_h * s->dev.img_w * 3, K = (size_t)n_variants;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    const size_t o_var = off; off += al(sizeof(LcrLookVar) * K);
-    const size_t o_bg = off; off += al(K * 2 * img);
-    const size_t o_cur = off; off += al(sizeof(int) * 10 * N);
-    const size_t o_term = off; off += al(sizeof(int) * 10 * N);
-    const size_t o_ep = off; off += al(sizeof(unsigned) * N);
-    size_t o_snap[2] = {off, off};
-    if (s->rstream) for (int p = 0; p < 2; p++) { o_snap[p] = off; off += al(sizeof(int) * 10 * N); }
+    Carver C;
+    const size_t o_var = C.take(sizeof(LcrLookVar) * K);
+    const size_t o_bg = C.take(K * 2 * img);
+    const size_t o_cur = C.take(sizeof(int) * 10 * N);
+    const size_t o_term = C.take(sizeof(int) * 10 * N);
+    const size_t o_ep = C.take(sizeof(unsigned) * N);
+    size_t o_snap[2] = {C.off, C.off};
+    if (s->rstream) for (int p = 0; p < 2; p++) o_snap[p] = C.take(sizeof(int) * 10 * N);
+    const size_t off = C.off;
     lcr_look_variant *copy = (lcr_look_variant *)malloc(sizeof(lcr_look_variant) * K);
     if (!copy) return fail(LCR_ERR_OOM, "host allocation failed");
     memcpy(copy, variants, sizeof(lcr_look_variant) * K);
@@ -1418,12 +1405,7 @@ int lcr_set_look(lcr_sim *s, const uint8_t *mask_host, const int32_t *variant_ho
             for (int j = 0; j < 9; j++) memcpy(&cur[(size_t)(1 + j) * N + i], rgb_host + (size_t)j * N + i, sizeof(float));
     }
     HIPCHK(hipMemcpy(s->look_cur, cur.data(), sizeof(int) * 10 * N, hipMemcpyHostToDevice));
-    int rc = launch_frames(s, s->dev, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (s->stack_on) {   // no time has passed: the newest slot of every env is rewritten
-        rc = launch_stack(s, s->stream, nullptr, LCR_STACK_NEWEST);
-        if (rc) return fail(LCR_ERR_HIP, "stack kernel launch failed: %s", rc < 0 ? "bad arguments" : hipGetErrorString((hipError_t)rc));
-    }
+    if (int rc = frames_after(s, s->dev, s->stream, nullptr, nullptr, LCR_STACK_NEWEST)) return rc;   // no time has passed: the newest slot of every env is rewritten
     HIPCHK(hipStreamSynchronize(s->stream));
     return LCR_OK;
 }
@@ -1501,13 +1483,17 @@ int lcr_enable_wrist_camera(lcr_sim *s, const lcr_wrist_camera *cam) {
     if (s->stack_on) return fail(LCR_ERR_INVALID, "the observation stack is enabled already: enable the wrist camera first and the stack last");
     if (s->planes) return fail(LCR_ERR_INVALID, "the image planes are enabled already: enable the wrist camera first and the planes second (they then cover it)");
     // the frames between two guard regions (include/lcr.h: LCR_WRIST_GUARD)
-    const size_t bytes = (((size_t)s->dev.n * s->dev.img_h * s->dev.img_w * 3 + 255) & ~(size_t)255) + 2 * LCR_WRIST_GUARD;
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_img = C.take((size_t)s->dev.n * s->dev.img_h * s->dev.img_w * 3);
+    C.skip(LCR_WRIST_GUARD);
+    const size_t bytes = C.off;
     void *mem = nullptr;
     hipError_t e = hipMalloc(&mem, bytes);
     if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the wrist frames failed: %s", bytes, hipGetErrorString(e));
     LcrWrist WR{};
     WR.mount = M;
-    WR.img = (unsigned char *)mem + LCR_WRIST_GUARD;
+    WR.img = (unsigned char *)mem + o_img;
     int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, bytes, s->stream);
     if (!rc) rc = lcr_launch_render_wrist(s->dev, WR, s->look_K ? &s->look : nullptr, s->stream);
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
@@ -1540,42 +1526,19 @@ int lcr_render_terminal_wrist(lcr_sim *s, const int32_t *env_ids_host, int count
     if (!s->wrist_on) return fail(LCR_ERR_INVALID, "no wrist camera is enabled on this sim (lcr_enable_wrist_camera)");
     if (count < 0 || (count > 0 && (!env_ids_host || !rgb_host))) return fail(LCR_ERR_INVALID, "NULL argument");
     if ((depth_host && !s->wrist.depth) || (seg_host && !s->wrist.seg)) return fail(LCR_ERR_INVALID, "a plane that is not enabled was asked for (lcr_enable_image_planes)");
-    for (int i = 0; i < count; i++)
-        if (env_ids_host[i] < 0 || env_ids_host[i] >= s->dev.n) return fail(LCR_ERR_INVALID, "env id %d out of range", env_ids_host[i]);
-    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, per_env = img + (depth_host ? px * sizeof(float) : 0) + (seg_host ? px : 0);
-    const size_t BUDGET = (size_t)450 << 20;   // bytes of frame staging per pass, as lcr_render_terminal
-    const size_t chunk = BUDGET / per_env;
-    const int cap = (size_t)count < chunk ? count : (int)chunk;
-    if (cap == 0) return LCR_OK;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off = 0;
-    const size_t o_ids = off; off += al(sizeof(int) * cap);
-    const size_t o_q = off; off += al(sizeof(float) * s->nq * cap);
-    const size_t o_t = off; off += al(sizeof(float) * 3 * cap);
-    const size_t o_f = off; off += al(img * cap);
-    const size_t o_d = off; if (depth_host) off += al(px * sizeof(float) * cap);
-    const size_t o_s = off; if (seg_host) off += al(px * cap);
-    const size_t o_lk = off; if (s->look_K) off += al(sizeof(int) * 10 * cap);   // the terminal looks of the listed envs
-    if (int rc = term_stage_reserve(s, off)) return rc;
-    char *base = (char *)s->term_stage;
-    for (int done = 0; done < count; done += cap) {
-        const int c = count - done < cap ? count - done : cap;
-        LcrDev P1;   // a `c`-env view of the handle whose state arrays are the gathered terminal poses
-        LcrLook LK;  // ... drawn, with a look, as the episodes that ended looked
-        int rc = term_stage_gather(s, env_ids_host + done, c, base, o_ids, o_q, o_t, o_lk, P1, LK);
-        if (rc) return rc;
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, dpx = depth_host ? px * sizeof(float) : 0, spx = seg_host ? px : 0;
+    const size_t per_env[] = {img, dpx, spx};   // the colours, the depth, the segmentation
+    return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
         LcrWrist W1 = s->wrist;
-        W1.img = (unsigned char *)(base + o_f);
-        W1.depth = depth_host ? (float *)(base + o_d) : nullptr;
-        W1.seg = seg_host ? (unsigned char *)(base + o_s) : nullptr;
-        rc = lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream);
-        if (rc) return fail(LCR_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)rc));
-        HIPCHK(hipMemcpyAsync(rgb_host + (size_t)done * img, base + o_f, img * c, hipMemcpyDeviceToHost, s->stream));
-        if (depth_host) HIPCHK(hipMemcpyAsync(depth_host + (size_t)done * px, base + o_d, px * sizeof(float) * c, hipMemcpyDeviceToHost, s->stream));
-        if (seg_host) HIPCHK(hipMemcpyAsync(seg_host + (size_t)done * px, base + o_s, px * c, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    return LCR_OK;
+        W1.img = (unsigned char *)buf[0];
+        W1.depth = (float *)buf[1];
+        W1.seg = (unsigned char *)buf[2];
+        LAUNCHCHK("render", lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream));
+        HIPCHK(hipMemcpyAsync(rgb_host + done * img, buf[0], img * c, hipMemcpyDeviceToHost, s->stream));
+        if (depth_host) HIPCHK(hipMemcpyAsync(depth_host + done * px, buf[1], dpx * c, hipMemcpyDeviceToHost, s->stream));
+        if (seg_host) HIPCHK(hipMemcpyAsync(seg_host + done * px, buf[2], spx * c, hipMemcpyDeviceToHost, s->stream));
+        return LCR_OK;
+    });
 }
 
 // ---- the observation stack ----
@@ -1611,17 +1574,20 @@ int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
     if (sp.cameras & LCR_STACK_CAM_WRIST) A.src[A.ncam++] = s->wrist.img;
     const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w, esize = sp.dtype == LCR_STACK_UINT8 ? 1 : sp.dtype == LCR_STACK_FLOAT16 ? 2 : 4;
     const size_t per_env = (size_t)sp.frames * 3 * A.ncam * px * esize;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // guard, stack, guard (include/lcr.h: LCR_WRIST_GUARD), then the two snapshots of did_reset
-    size_t off = LCR_WRIST_GUARD + al(N * per_env) + LCR_WRIST_GUARD;
-    const size_t guarded = off;
-    size_t o_snap[2] = {off, off};
-    if (s->rstream) for (int p = 0; p < 2; p++) { o_snap[p] = off; off += al(N); }
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_dst = C.take(N * per_env);
+    C.skip(LCR_WRIST_GUARD);
+    const size_t guarded = C.off;
+    size_t o_snap[2] = {C.off, C.off};
+    if (s->rstream) for (int p = 0; p < 2; p++) o_snap[p] = C.take(N);
+    const size_t off = C.off;
     void *mem = nullptr;
     hipError_t e = hipMalloc(&mem, off);
     if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the observation stack failed: %s", off, hipGetErrorString(e));
     char *base = (char *)mem;
-    A.dst = base + LCR_WRIST_GUARD;
+    A.dst = base + o_dst;
     A.n = s->dev.n; A.pixels = (int)px; A.frames = sp.frames; A.dtype = sp.dtype;
     A.zero_fill = sp.reset_fill == LCR_STACK_FILL_ZERO;
     A.flags = nullptr; A.op = LCR_STACK_REFILL;
@@ -1659,8 +1625,7 @@ int lcr_calibrate_copy(lcr_sim *s, float *dst_dev, size_t n_floats) {
     SIMCHK(s);
     if (!dst_dev) return fail(LCR_ERR_INVALID, "dst is NULL");
     if (n_floats * sizeof(float) > s->arena_bytes) return fail(LCR_ERR_INVALID, "n_floats exceeds the state arena (%zu bytes)", s->arena_bytes);
-    int rc = lcr_launch_calib_copy((const float *)s->arena, dst_dev, n_floats, s->stream);
-    if (rc) return fail(LCR_ERR_HIP, "calibration kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    LAUNCHCHK("calibration kernel", lcr_launch_calib_copy((const float *)s->arena, dst_dev, n_floats, s->stream));
     return LCR_OK;
 }
 

@@ -382,12 +382,17 @@ class VecSim:
         check(self.L.lcr_render_state(self.handle, cam, int(width), int(height), _vp(q), _vp(t), _vp(out)))
         return out
 
+    def _finished_ids(self, name, env_ids):
+        """env_ids as the int32 array the render_terminal* call `name` hands to the library, checked against that call's precondition"""
+        ids = np.ascontiguousarray(env_ids, np.int32)
+        if ids.size and self.image_front is not None and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():   # (lcr.h: the terminal poses belong to envs the LAST step reset; anything else is a stale frame)
+            raise ValueError(f"{name}: every listed env must have finished an episode in the last step (did_reset)")
+        return ids
+
     def render_terminal(self, env_ids):
         """last frames (camera_front, camera_top) of the episodes the last step ended in the listed envs, ray-cast as ONE batch from their
         terminal poses (the envs themselves have already been reset): two (len(env_ids), H, W, 3) uint8 arrays, (H, W) = self.image_size"""
-        ids = np.ascontiguousarray(env_ids, np.int32)
-        if ids.size and self.image_front is not None and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():   # (lcr.h: the terminal poses belong to envs the LAST step reset; anything else is a stale frame)
-            raise ValueError("render_terminal: every listed env must have finished an episode in the last step (did_reset)")
+        ids = self._finished_ids("render_terminal", env_ids)
         front = np.empty((ids.size,) + self.image_size + (3,), np.uint8)
         top = np.empty_like(front)
         check(self.L.lcr_render_terminal(self.handle, _vp(ids), int(ids.size), _vp(front), _vp(top)))
@@ -398,9 +403,7 @@ class VecSim:
         keys of observations() -- image_wrist (len(env_ids), H, W, 3) uint8 and, with image_planes, depth_wrist float32 / segmentation_wrist uint8 (len(env_ids), H, W)"""
         if self.wrist_camera is None:
             raise ValueError("render_terminal_wrist: no wrist_camera is enabled")
-        ids = np.ascontiguousarray(env_ids, np.int32)
-        if ids.size and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():
-            raise ValueError("render_terminal_wrist: every listed env must have finished an episode in the last step (did_reset)")
+        ids = self._finished_ids("render_terminal_wrist", env_ids)
         shape = (ids.size,) + self.image_size
         rgb = np.empty(shape + (3,), np.uint8)
         d = np.empty(shape, np.float32) if self.depth_wrist is not None else None
@@ -457,9 +460,7 @@ class VecSim:
         a dict with the keys of observations() -- depth_front, depth_top (len(env_ids), H, W) float32 / segmentation_front, segmentation_top uint8"""
         if not self.image_planes:
             raise ValueError("render_terminal_planes: no image_planes are enabled")
-        ids = np.ascontiguousarray(env_ids, np.int32)
-        if ids.size and ids.min() >= 0 and ids.max() < self.n and not self.did_reset.numpy()[ids].all():
-            raise ValueError("render_terminal_planes: every listed env must have finished an episode in the last step (did_reset)")
+        ids = self._finished_ids("render_terminal_planes", env_ids)
         shape = (ids.size,) + self.image_size
         d = "depth" in self.image_planes
         s = "segmentation" in self.image_planes
