@@ -36,6 +36,10 @@ STACK_CAMERAS = {"front": 1, "top": 2, "wrist": 4}
 STACK_DTYPES = {"uint8": 0, "float16": 1, "float32": 2}
 STACK_FILLS = {"repeat": 0, "zero": 1}
 STACK_MAX_FRAMES = 8
+# the point cloud (lcr_enable_point_cloud): its cameras are STACK_CAMERAS bits; the surface ids of the segmentation plane by name ("arm": base_link, link_1 .. link_6)
+CLOUD_IDS = {"floor": 1 << 1, "arm": 0x7F << 2, "cube": 1 << 9, "cube2": 1 << 10}
+CLOUD_DEFAULT_IDS = 0x7FC   # LCR_CLOUD_DEFAULT_IDS: arm, cube, cube2
+CLOUD_MIN_POINTS, CLOUD_MAX_POINTS = 64, 8192
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -51,6 +55,7 @@ SYMBOLS = [
     "lcr_look_variant_default", "lcr_enable_look", "lcr_set_look", "lcr_get_look",
     "lcr_wrist_camera_default", "lcr_wrist_camera_check", "lcr_enable_wrist_camera", "lcr_get_wrist_camera", "lcr_render_terminal_wrist",
     "lcr_obs_stack_check", "lcr_enable_obs_stack", "lcr_get_obs_stack",
+    "lcr_point_cloud_check", "lcr_enable_point_cloud", "lcr_get_point_cloud",
 ]
 
 
@@ -313,6 +318,78 @@ class LcrObsStackView(ctypes.Structure):
     ]
 
 
+class PointCloudSpec(ctypes.Structure):
+    """lcr_point_cloud_spec: points per env, cameras, surface ids and channels of the point cloud (include/lcr.h)"""
+    _fields_ = [
+        ("points", ctypes.c_int32),      # P, a multiple of 64 in 64 .. 8192
+        ("cameras", ctypes.c_uint32),    # STACK_CAMERAS bits; 0 = every camera the handle has
+        ("ids", ctypes.c_uint32),        # bit i: surface id i is a candidate (1 .. 10); 0 = CLOUD_DEFAULT_IDS
+        ("colors", ctypes.c_int32),      # 0: x y z, 1: x y z r g b
+    ]
+
+    def as_dict(self):
+        return {"points": int(self.points), "cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b),
+                "ids": tuple(i for i in range(32) if self.ids >> i & 1), "colors": bool(self.colors)}
+
+    @classmethod
+    def from_any(cls, v):
+        """a PointCloudSpec, an int (that many points of every camera, arm and cubes, x y z), or a dict of some of points / cameras / ids / colors"""
+        import numpy as np
+
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer, dict)):
+            raise ValueError(f"point_cloud must be None, a number of points or a dict of points / cameras / ids / colors, got {v!r}")
+        v = {"points": v} if not isinstance(v, dict) else dict(v)
+        out = cls()
+        points = v.pop("points", 1024)
+        if isinstance(points, (bool, np.bool_)) or not isinstance(points, (int, np.integer)) or not CLOUD_MIN_POINTS <= points <= CLOUD_MAX_POINTS or points % 64:
+            raise ValueError(f"point_cloud: points must be a multiple of 64 in {CLOUD_MIN_POINTS} .. {CLOUD_MAX_POINTS}, got {points!r}")
+        out.points = int(points)
+        cams = v.pop("cameras", None)
+        if cams is not None:
+            if isinstance(cams, str) or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"point_cloud: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        ids = v.pop("ids", None)
+        if ids is not None:
+            mask = 0
+            ok = not isinstance(ids, str) and hasattr(ids, "__iter__")
+            for i in (ids if ok else ()):
+                if isinstance(i, str) and i in CLOUD_IDS:
+                    mask |= CLOUD_IDS[i]
+                elif isinstance(i, (int, np.integer)) and not isinstance(i, (bool, np.bool_)) and 1 <= i <= 10:
+                    mask |= 1 << int(i)
+                else:
+                    ok = False
+            if not ok or mask == 0:
+                raise ValueError(f"point_cloud: ids must be a non-empty tuple drawn from 'arm', 'cube', 'cube2', 'floor' and the surface ids 1 .. 10, got {ids!r}")
+            out.ids = mask
+        colors = v.pop("colors", False)
+        if not isinstance(colors, (bool, np.bool_)):
+            raise ValueError(f"point_cloud: colors must be a bool, got {colors!r}")
+        out.colors = int(colors)
+        if v:
+            raise ValueError(f"unknown point_cloud fields {sorted(v)}")
+        return out
+
+
+class LcrPointCloudView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", PointCloudSpec),        # cameras and ids resolved to the bits in use
+        ("channels", ctypes.c_int32),
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("points", ctypes.c_void_p),       # [N][P][C] float32
+        ("count", ctypes.c_void_p),        # [N] int32
+        ("source", ctypes.c_void_p),       # [N][P] int32
+        ("camera_pose", ctypes.c_void_p),  # [slots][13][N] float32
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -437,6 +514,9 @@ def load():
     L.lcr_obs_stack_check.argtypes = [ctypes.POINTER(ObsStackSpec)]
     L.lcr_enable_obs_stack.argtypes = [vp, ctypes.POINTER(ObsStackSpec)]
     L.lcr_get_obs_stack.argtypes = [vp, ctypes.POINTER(LcrObsStackView)]
+    L.lcr_point_cloud_check.argtypes = [ctypes.POINTER(PointCloudSpec)]
+    L.lcr_enable_point_cloud.argtypes = [vp, ctypes.POINTER(PointCloudSpec)]
+    L.lcr_get_point_cloud.argtypes = [vp, ctypes.POINTER(LcrPointCloudView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

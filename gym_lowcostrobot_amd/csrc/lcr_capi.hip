@@ -14,6 +14,7 @@
 #include "lcr_device.h"
 #include "lcr_model_gen.h"
 #include "lcr_stack.h"
+#include "lcr_cloud.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -176,6 +177,11 @@ struct lcr_sim {
     void *stack_mem;
     size_t stack_bytes_per_env;
     unsigned char *snap_reset[2];      // beside snap_qpos / snap_target / snap_look
+    // the point cloud (lcr_enable_point_cloud): one allocation -- guard, points, guard, count, source, camera poses --, fixed for the life of the handle
+    bool cloud_on;
+    lcr_point_cloud_spec cloud_spec;   // as enabled, cameras and ids resolved
+    LcrCloud cloud;                    // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
+    void *cloud_mem;
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -208,11 +214,22 @@ static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *fla
     return lcr_launch_obs_stack(A, stream);
 }
 
-// frames, then stack: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
-// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack)
+// the cloud kernel, behind the frame kernels (and the stack kernel) on their stream: the cloud of P's envs from the frames just drawn, with the cameras that drew them --
+// the handle's or, with a look, those of the envs' variants (`look` as in look_args) -- and the wrist pose from P's qpos, the pose snapshot the wrist frames were drawn from
+static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
+    LcrCloud A = s->cloud;
+    A.front = s->cam_front; A.top = s->cam_top;
+    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
+    A.qpos = P.qpos;
+    return lcr_launch_point_cloud(A, stream);
+}
+
+// frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
+// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), and on a handle with a point cloud its kernel last
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op));
+    if (s->cloud_on) LAUNCHCHK("point-cloud kernel", launch_cloud(s, P, stream, look));
     return LCR_OK;
 }
 
@@ -704,6 +721,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->look_mem) (void)hipFree(s->look_mem);
     if (s->wrist_mem) (void)hipFree(s->wrist_mem);
     if (s->stack_mem) (void)hipFree(s->stack_mem);
+    if (s->cloud_mem) (void)hipFree(s->cloud_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -1618,6 +1636,98 @@ int lcr_get_obs_stack(lcr_sim *s, lcr_obs_stack_view *out) {
     out->image_height = s->dev.img_h;
     out->data = s->stack.dst;
     out->bytes_per_env = (uint64_t)s->stack_bytes_per_env;
+    return LCR_OK;
+}
+
+// ---- the point cloud ----
+
+int lcr_point_cloud_check(const lcr_point_cloud_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (spec->points < 64 || spec->points > 8192 || spec->points % 64 != 0) return fail(LCR_ERR_INVALID, "points must be a multiple of 64 in 64 .. 8192, got %d", spec->points);
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be a mask of 1 (front), 2 (top) and 4 (wrist), or 0 for every camera of the handle, got %u", spec->cameras);
+    if (spec->ids & ~(uint32_t)0x7FEu)
+        return fail(LCR_ERR_INVALID, "ids must be a mask over the surface ids 1 .. 10 (bits 1 .. 10; bit 0 is the sky, which is no surface), or 0 for arm and cubes (0x7FC), got 0x%x", spec->ids);
+    if (spec->colors != 0 && spec->colors != 1) return fail(LCR_ERR_INVALID, "colors must be 0 (x y z) or 1 (x y z r g b), got %d", spec->colors);
+    return LCR_OK;
+}
+
+int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) {
+    // the argument first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_point_cloud_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a point cloud of");
+    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
+    if ((s->planes & both) != both)
+        return fail(LCR_ERR_INVALID, "the point cloud needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the cloud): %s",
+                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
+    lcr_point_cloud_spec sp = *spec;
+    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
+    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the cloud)");
+    if (s->cloud_on) {
+        if (memcmp(&s->cloud_spec, &sp, sizeof sp) == 0) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d) is enabled already and fixed for the life of the handle", s->cloud_spec.points,
+                    s->cloud_spec.cameras, s->cloud_spec.ids, s->cloud_spec.colors);
+    }
+    LcrCloud A{};
+    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
+        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
+    };
+    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
+    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
+    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    const size_t N = (size_t)s->dev.n, P = (size_t)sp.points, Cn = sp.colors ? 6 : 3;
+    // guard, points, guard (include/lcr.h: LCR_WRIST_GUARD), then count, source and the camera poses
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_pts = C.take(N * P * Cn * sizeof(float));
+    C.skip(LCR_WRIST_GUARD);
+    const size_t guarded = C.off;
+    const size_t o_cnt = C.take(N * sizeof(int));
+    const size_t o_src = C.take(N * P * sizeof(int));
+    const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
+    const size_t off = C.off;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the point cloud failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.points = sp.points; A.channels = (int)Cn; A.ids = sp.ids;
+    A.out = (float *)(base + o_pts);
+    A.count = (int *)(base + o_cnt);
+    A.source = (int *)(base + o_src);
+    A.pose = (float *)(base + o_pose);
+    A.mount = s->wrist.mount;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    s->cloud = A;
+    if (!rc) rc = launch_cloud(s, s->dev, s->stream, nullptr);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->cloud = LcrCloud{}; return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); s->cloud = LcrCloud{}; return fail(LCR_ERR_HIP, "making the point cloud failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->cloud_mem = mem;
+    s->cloud_spec = sp;
+    s->cloud_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_point_cloud(lcr_sim *s, lcr_point_cloud_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the cloud is made behind the frames, on the second stream after a step: the handle's stream waits for it here)
+    memset(out, 0, sizeof *out);
+    if (!s->cloud_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->cloud_spec;
+    out->channels = s->cloud.channels;
+    out->slots = s->cloud.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->points = s->cloud.out;
+    out->count = s->cloud.count;
+    out->source = s->cloud.source;
+    out->camera_pose = s->cloud.pose;
+    out->bytes_per_env = (uint64_t)s->cloud.points * s->cloud.channels * sizeof(float);
     return LCR_OK;
 }
 

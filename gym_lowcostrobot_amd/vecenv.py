@@ -68,6 +68,9 @@ class LowCostRobotVecEnv(_SB3VecEnv):
     def __init__(self, task, num_envs, seed=0, device=0, env_id_offset=0, **kw):
         kw.setdefault("observation_mode", "state")
         self.observation_mode = kw["observation_mode"]
+        if kw.get("point_cloud") is not None:   # (as the observation stack)
+            raise ValueError("point_cloud is for on-device loops over VecSim: an env the step has auto-reset shows its reset state, so the cloud of the episode that ended is gone, "
+                             "and LowCostRobotVecEnv / LowCostRobotVectorEnv, which owe SB3 / gymnasium a complete terminal_observation, do not expose it")
         self.sim = VecSim(task, num_envs, device=device, env_id_offset=env_id_offset, base_seed=seed, auto_reset=True, **kw)
         self.num_envs = int(num_envs)
         self.task = task

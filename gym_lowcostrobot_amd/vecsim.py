@@ -42,7 +42,7 @@ class DeviceArray:
         return out
 
     def torch(self):
-        """zero-copy torch view; image views, planes, wrist frames and the stack are read on the handle's stream after VecSim.wait_frames() or any other joining call (lcr.h: lcr_step)"""
+        """zero-copy torch view; image views, planes, wrist frames, the stack and the point cloud are read on the handle's stream after VecSim.wait_frames() or any other joining call (lcr.h: lcr_step)"""
         import torch
 
         return torch.as_tensor(self, device=f"cuda:{self._sim.device}")
@@ -95,6 +95,7 @@ class VecSim:
         look_sampler=None,
         wrist_camera=None,
         obs_stack=None,
+        point_cloud=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -141,6 +142,17 @@ class VecSim:
             if obs_stack.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
                 raise ValueError("obs_stack: cameras selects 'wrist', but no wrist_camera is given")
             check(self.L.lcr_obs_stack_check(ctypes.byref(obs_stack)))
+        # the point cloud (lcr_enable_point_cloud): None = none, an int = that many points of every camera (arm and cubes, x y z), or a dict of points / cameras / ids / colors.
+        # Checked here and by the library without a handle (lcr_point_cloud_check), before it is asked for a device.  It is made of both planes: they are not switched on silently
+        if point_cloud is not None:
+            if observation_mode == "state":
+                raise ValueError("point_cloud needs image observations: observation_mode 'image' or 'both'")
+            point_cloud = _capi.PointCloudSpec.from_any(point_cloud)
+            if point_cloud.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("point_cloud: cameras selects 'wrist', but no wrist_camera is given")
+            if set(image_planes) != set(_capi.IMAGE_PLANES):
+                raise ValueError(f"point_cloud is made of the depth and the segmentation plane: pass both, image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_point_cloud_check(ctypes.byref(point_cloud)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -289,6 +301,21 @@ class VecSim:
                 raise
             self.obs_stack_spec = sv.spec.as_dict()
             self.obs_stack = DeviceArray(self, sv.data, (N, int(sv.spec.frames), int(sv.channels)) + self.image_size, np.dtype(self.obs_stack_spec["dtype"]))
+        self.point_cloud = self.point_cloud_count = self.point_cloud_source = self.point_cloud_pose = self.point_cloud_spec = None
+        if point_cloud is not None:   # (behind look, wrist camera and planes; before or after the stack)
+            try:
+                check(self.L.lcr_enable_point_cloud(self.handle, ctypes.byref(point_cloud)))
+                cv = _capi.LcrPointCloudView()
+                check(self.L.lcr_get_point_cloud(self.handle, ctypes.byref(cv)))
+            except Exception:
+                self.close()
+                raise
+            self.point_cloud_spec = cv.spec.as_dict()
+            P = int(cv.spec.points)
+            self.point_cloud = DeviceArray(self, cv.points, (N, P, int(cv.channels)), np.float32)
+            self.point_cloud_count = DeviceArray(self, cv.count, (N,), np.int32)
+            self.point_cloud_source = DeviceArray(self, cv.source, (N, P), np.int32)
+            self.point_cloud_pose = DeviceArray(self, cv.camera_pose, (int(cv.slots), 13, N), np.float32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -327,7 +354,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -534,6 +561,8 @@ class VecSim:
                 obs[k] = a.numpy()
             if self.obs_stack is not None:
                 obs["image_stack"] = self.obs_stack.numpy()
+            if self.point_cloud is not None:
+                obs["point_cloud"] = self.point_cloud.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

@@ -515,6 +515,64 @@ int lcr_enable_obs_stack(lcr_sim *sim, const lcr_obs_stack_spec *spec);
 /* The stack; waits (on the handle's stream) for frames and stack still being made on the second stream, as every entry point but the step does. */
 int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
 
+/* == The point cloud: an optional device buffer per handle, `points` [N][P][C] float32, that the library keeps current behind the frame kernels -- a fixed number of
+ * world-frame points per env, fused over the cameras, floor and sky dropped: the input of a PointNet-style encoder or a 3-D diffusion policy.  Everything it is made of
+ * lies in device memory after the frame kernels (depth along a known ray, surface ids, colours, the cameras); the kernel compacts a variable number of surface pixels per
+ * env to a fixed count and unprojects them with the cameras that drew them, in stream order, without a host round trip.  Off by default: without
+ * lcr_enable_point_cloud no byte, state, output or kernel of the handle changes.
+ *   cameras     a mask of LCR_STACK_CAM_* bits; 0 = every camera the handle has.  Camera SLOTS are the selected cameras in the order front, top, wrist.  The wrist bit on
+ *               a handle without a wrist camera is refused.
+ *   candidates  a pixel of a selected camera whose segmentation byte has id = byte & 0x7f with bit `id` set in `ids` (the marker bit 7 is ignored).  `ids` is a mask over
+ *               the ids 1 .. 10; 0 means 0x7FC: the arm's seven boxes and the cubes, without the floor.  Bit 0 (sky: no surface) and bits above 10 are refused.
+ *               Candidates are numbered 0 .. M - 1 by camera slot, then row-major pixel.
+ *   selection   deterministic, one rule for every M: output point j (0 <= j < P) is candidate ((2 j + 1) M) / (2 P), an integer division in 64 bits (the product exceeds
+ *               2^32).  M >= P: an even stride through the candidates; 0 < M < P: candidates repeat monotonically, each at least floor(P / M) times; M = 0: zeros in
+ *               all of the env's points and -1 in its sources.
+ *   point       of a candidate at (row, px) of a camera with position ro, world axes X, Y, Z and ray scale s: the ray of the planes section, d = sx X + sy Y - Z with
+ *               sx, sy exactly as the colour and plane kernels form them; p = ro + t d with t the float32 depth plane value, in the WORLD frame.  A surface beyond
+ *               depth_far sits at depth_far along its ray: documented, not filtered (the default 10 m is beyond every scene).
+ *   channels    C = 3: x y z.  C = 6 (colors = 1): x y z r g b, the colours from the colour frame as (float)x * (1.0f / 255.0f), the stack's float32 rule, bit for bit.
+ *   count       [N] int32: M.
+ *   source      [N][P] int32: slot H W + row W + px of the chosen candidate, or -1.  A policy can gather per-pixel features with it.
+ *   camera_pose [slots][13][N] float32: ro, X, Y, Z, s of every slot per env as the kernel used them -- the cloud's extrinsics, which a caller who fuses views needs as
+ *               well.  Front and top are the handle's cameras or the env's look variant's; the wrist pose comes from the link chain of the same pose snapshot the wrist
+ *               frames were drawn from, computed by the device code the wrist kernel uses.
+ *   P           `points`: a multiple of 64 in 64 .. 8192.
+ *   invariant   after every entry point that draws the batched frames -- lcr_step, lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- cloud, count,
+ *               source and pose are the function above of that env's current frames, planes and cameras.  No history and no reset rule: an auto-reset env shows its reset
+ *               state, as its frames do.
+ *   ordering    the cloud kernel runs behind the frame kernels (and the stack kernel, if there is one) on whatever stream they ran on; the event the joining entry points
+ *               wait for is recorded after it.  After a step on the second stream it reads the look snapshot and the pose snapshot the frames used.
+ *   life        needs image observations and BOTH planes; since look and wrist camera refuse to come after the planes, the cloud is enabled after all three, before or
+ *               after the observation stack.  Fixed for the life of the handle: the same spec again does nothing, another spec is refused.
+ *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, points, the same guard from the first 256-byte boundary at or behind their end (as the
+ *               stack has them), then count, source and camera_pose.  Freed by lcr_destroy.
+ *   not in it   a crop box, random or farthest-point sampling, normals, a base-frame transform, the cloud of an episode that has ended. */
+typedef struct lcr_point_cloud_spec {
+    int32_t points;       /* P: a multiple of 64 in 64 .. 8192 */
+    uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+    uint32_t ids;         /* bit i: surface id i is a candidate, i = 1 .. 10; 0 = 0x7FC (arm and cubes) */
+    int32_t colors;       /* 0: C = 3 (x y z); 1: C = 6 (x y z r g b) */
+} lcr_point_cloud_spec;
+typedef struct lcr_point_cloud_view {
+    int32_t enabled;                   /* 0: no cloud, everything below is 0 / NULL */
+    lcr_point_cloud_spec spec;         /* as enabled, `cameras` and `ids` resolved to the bits in use */
+    int32_t channels, slots, image_width, image_height;
+    const float *points;               /* device, [N][P][C] */
+    const int32_t *count;              /* device, [N] */
+    const int32_t *source;             /* device, [N][P] */
+    const float *camera_pose;          /* device, [slots][13][N] */
+    uint64_t bytes_per_env;            /* P C sizeof(float) */
+} lcr_point_cloud_view;
+#define LCR_CLOUD_DEFAULT_IDS 0x7FCu
+/* The checks lcr_enable_point_cloud makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field's name in the message */
+int lcr_point_cloud_check(const lcr_point_cloud_spec *spec);
+/* Switch the cloud on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without both planes and a wrist bit without a wrist camera
+ * are refused (LCR_ERR_INVALID, naming what is missing); an allocation that fails is LCR_ERR_OOM.  Makes the cloud of the current frames. */
+int lcr_enable_point_cloud(lcr_sim *sim, const lcr_point_cloud_spec *spec);
+/* The cloud; waits (on the handle's stream) for frames and cloud still being made on the second stream, as every entry point but the step does. */
+int lcr_get_point_cloud(lcr_sim *sim, lcr_point_cloud_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */

@@ -1,5 +1,5 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist]
+    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist] [--cloud[=P]]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
@@ -12,6 +12,10 @@ from -- K cached background pairs instead of one.
 --wrist: ONLY the wrist camera (VecSim(wrist_camera=True), the default mount), at 84x84, 128x128 and 240x320, two rounds of [without, with] in turn: (i) of a sim without it
 (the two-camera frame kernel) and of a sim with it (both kernels, back to back on one stream), the wrist kernel's time as the difference of the two, the bytes either kernel
 writes per ms; (ii) env-steps/s closed and open loop, without and with the camera.
+--cloud[=P]: ONLY the point cloud (VecSim(point_cloud=P), default 1024 points, front + top, arm and cubes, x y z), at the four sizes, two rounds of [without, with] in turn:
+(i) of a sim with both planes and no cloud (the frame kernel) and of a sim with the cloud (frame kernel and cloud kernel back to back on one stream), the cloud kernel's
+time as the difference of the two, the bytes it reads by the model of DESIGN.md section 3.4 -- one segmentation byte per pixel and camera, and per point the 16 id bytes of
+its group again, one depth float (with colours three bytes more) -- and the TB/s that makes.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -24,14 +28,16 @@ from gym_lowcostrobot_amd import VecSim  # noqa: E402
 
 PLANES = "--planes" in sys.argv
 WRIST = "--wrist" in sys.argv
+CLOUD = [a for a in sys.argv[1:] if a == "--cloud" or a.startswith("--cloud=")]
+CLOUD_P = int(CLOUD[0].split("=")[1]) if CLOUD and "=" in CLOUD[0] else 1024
 LOOK = [int(k) for k in sys.argv[sys.argv.index("--look") + 1].split(",")] if "--look" in sys.argv else []
-args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--planes", "--look", "--wrist") and sys.argv[i - 1] != "--look"]
+args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ["--planes", "--look", "--wrist"] + CLOUD and sys.argv[i - 1] != "--look"]
 n = int(args[0]) if len(args) > 0 else 32768
 task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
 SOAK_S, WINDOWS, STEPS = 2.0, 7, 60
 print(f"frame sizes: {task}, {n} envs, default preset, LCR_RENDER_EPW={os.environ.get('LCR_RENDER_EPW', '(by frame size)')}")
-if not WRIST:
+if not WRIST and not CLOUD:
     print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
 rows = []
 
@@ -128,6 +134,33 @@ if WRIST:
                           f"{nb / 2 / wr / 1e9:5.2f} TB/s   steps/s {closed:.3e} / {opened:.3e}", flush=True)
                 for a in act:
                     sim.free(a)
+                sim.close()
+    sys.exit(0)
+
+if CLOUD:
+    slots, C = 2, 3
+    print(f"the point cloud ({n} envs, P = {CLOUD_P}, front + top, arm and cubes, x y z): ms per launch (median of {WINDOWS} windows of ten; min max), GB read by the model, TB/s")
+    for H, W in SIZES:
+        for rnd in (1, 2):
+            base = None
+            for on in (False, True):
+                sim = VecSim(task, n, observation_mode="both", image_size=(H, W), image_planes=("depth", "segmentation"), **({"point_cloud": CLOUD_P} if on else {}))
+                act = sim.alloc_actions()
+                for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+                    sim.fill_random_actions(act, 1, t % 8)
+                    sim.step_device(act.ptr)
+                ms, wmin, wmax = frame_kernel_ms(sim)
+                if not on:
+                    base = ms
+                    print(f"{H:4d}x{W:<4d} round {rnd} frame kernel with planes   {ms:7.3f} ({wmin:.3f} {wmax:.3f})  {2 * H * W * 8 * n / ms / 1e9:5.2f} TB/s written", flush=True)
+                else:
+                    cl = ms - base
+                    mean_m = float(sim.point_cloud_count.numpy().mean())
+                    rd = n * (slots * H * W + CLOUD_P * (16 + 4)) + 0.0
+                    wr = n * CLOUD_P * (4 * C + 4)
+                    print(f"{H:4d}x{W:<4d} round {rnd} frame + cloud kernel       {ms:7.3f} ({wmin:.3f} {wmax:.3f})  cloud kernel (difference) {cl:6.3f} ms = {cl / base:.3f} of the frame kernel  "
+                          f"reads {rd / 1e9:6.3f} GB -> {rd / cl / 1e9:5.2f} TB/s read, writes {wr / 1e9:.3f} GB; mean M {mean_m:.0f}", flush=True)
+                sim.free(act)
                 sim.close()
     sys.exit(0)
 
