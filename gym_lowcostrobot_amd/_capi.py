@@ -40,6 +40,8 @@ STACK_MAX_FRAMES = 8
 CLOUD_IDS = {"floor": 1 << 1, "arm": 0x7F << 2, "cube": 1 << 9, "cube2": 1 << 10}
 CLOUD_DEFAULT_IDS = 0x7FC   # LCR_CLOUD_DEFAULT_IDS: arm, cube, cube2
 CLOUD_MIN_POINTS, CLOUD_MAX_POINTS = 64, 8192
+CLOUD_SAMPLINGS = {"stride": 0, "fps": 1}   # LCR_CLOUD_SAMPLE_*: the strided selection, or farthest-point sampling from a strided pool (lcr_enable_point_cloud_sampled)
+CLOUD_MAX_POOL = 4096                       # LCR_CLOUD_MAX_POOL
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -56,6 +58,7 @@ SYMBOLS = [
     "lcr_wrist_camera_default", "lcr_wrist_camera_check", "lcr_enable_wrist_camera", "lcr_get_wrist_camera", "lcr_render_terminal_wrist",
     "lcr_obs_stack_check", "lcr_enable_obs_stack", "lcr_get_obs_stack",
     "lcr_point_cloud_check", "lcr_enable_point_cloud", "lcr_get_point_cloud",
+    "lcr_point_cloud_sampling_check", "lcr_enable_point_cloud_sampled", "lcr_get_point_cloud_sampling",
 ]
 
 
@@ -374,6 +377,41 @@ class PointCloudSpec(ctypes.Structure):
         return out
 
 
+class PointCloudSampling(ctypes.Structure):
+    """lcr_point_cloud_sampling: how the cloud's points are picked -- the strided rule, or farthest-point sampling (FPS) out of a strided pool (include/lcr.h)"""
+    _fields_ = [
+        ("mode", ctypes.c_int32),        # CLOUD_SAMPLINGS
+        ("pool", ctypes.c_int32),        # Q under "fps": a multiple of 64, points <= pool <= CLOUD_MAX_POOL; 0 under "stride"
+    ]
+
+    def as_dict(self):
+        return {"mode": {v: k for k, v in CLOUD_SAMPLINGS.items()}.get(int(self.mode), int(self.mode)), "pool": int(self.pool)}
+
+    @classmethod
+    def take(cls, v):
+        """(what is left of the point_cloud argument, its PointCloudSampling): takes `sampling` and `pool` out of a dict; anything else is a strided cloud"""
+        import numpy as np
+
+        out = cls()
+        if not isinstance(v, dict) or not ("sampling" in v or "pool" in v):
+            return v, out
+        v = dict(v)
+        sampling, pool = v.pop("sampling", "stride"), v.pop("pool", None)
+        if not isinstance(sampling, str) or sampling not in CLOUD_SAMPLINGS:
+            raise ValueError(f"point_cloud: sampling must be 'stride' or 'fps', got {sampling!r}")
+        out.mode = CLOUD_SAMPLINGS[sampling]
+        if sampling == "stride":
+            if pool is not None:
+                raise ValueError(f"point_cloud: pool goes with sampling='fps' (a strided cloud has no pool), got pool {pool!r}")
+            return v, out
+        if pool is None:
+            raise ValueError("point_cloud: sampling='fps' needs a pool (the candidates the points are picked from: the caller chooses the cost)")
+        if isinstance(pool, (bool, np.bool_)) or not isinstance(pool, (int, np.integer)) or not 64 <= pool <= CLOUD_MAX_POOL or pool % 64:
+            raise ValueError(f"point_cloud: pool must be a multiple of 64 in 64 .. {CLOUD_MAX_POOL}, got {pool!r}")
+        out.pool = int(pool)
+        return v, out
+
+
 class LcrPointCloudView(ctypes.Structure):
     _fields_ = [
         ("enabled", ctypes.c_int32),
@@ -517,6 +555,9 @@ def load():
     L.lcr_point_cloud_check.argtypes = [ctypes.POINTER(PointCloudSpec)]
     L.lcr_enable_point_cloud.argtypes = [vp, ctypes.POINTER(PointCloudSpec)]
     L.lcr_get_point_cloud.argtypes = [vp, ctypes.POINTER(LcrPointCloudView)]
+    L.lcr_point_cloud_sampling_check.argtypes = [ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling)]
+    L.lcr_enable_point_cloud_sampled.argtypes = [vp, ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling)]
+    L.lcr_get_point_cloud_sampling.argtypes = [vp, ctypes.POINTER(PointCloudSampling)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

@@ -181,6 +181,7 @@ struct lcr_sim {
     bool cloud_on;
     lcr_point_cloud_spec cloud_spec;   // as enabled, cameras and ids resolved
     LcrCloud cloud;                    // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
+    lcr_point_cloud_sampling cloud_sampling;   // stride, or farthest-point sampling from a pool (lcr_enable_point_cloud_sampled): which kernel makes the cloud
     void *cloud_mem;
 };
 
@@ -221,6 +222,7 @@ static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     A.front = s->cam_front; A.top = s->cam_top;
     if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
     A.qpos = P.qpos;
+    if (s->cloud_sampling.mode == LCR_CLOUD_SAMPLE_FPS) return lcr_launch_point_cloud_fps(LcrCloudFps{A, s->cloud_sampling.pool}, stream);
     return lcr_launch_point_cloud(A, stream);
 }
 
@@ -1652,9 +1654,32 @@ int lcr_point_cloud_check(const lcr_point_cloud_spec *spec) {
     return LCR_OK;
 }
 
-int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) {
-    // the argument first, the handle afterwards (what can be refused without a device is)
+static const char *cloud_mode_name(int mode) { return mode == LCR_CLOUD_SAMPLE_FPS ? "fps" : "stride"; }
+
+int lcr_point_cloud_sampling_check(const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (!sampling) return fail(LCR_ERR_INVALID, "sampling is NULL");
+    if (sampling->mode != LCR_CLOUD_SAMPLE_STRIDE && sampling->mode != LCR_CLOUD_SAMPLE_FPS)
+        return fail(LCR_ERR_INVALID, "mode must be 0 (stride) or 1 (farthest-point sampling), got %d", sampling->mode);
+    if (sampling->mode == LCR_CLOUD_SAMPLE_STRIDE) {
+        if (sampling->pool != 0) return fail(LCR_ERR_INVALID, "pool must be 0 with mode 0 (stride): a strided cloud has no pool, got %d", sampling->pool);
+        return LCR_OK;
+    }
+    if (sampling->pool < 64 || sampling->pool > LCR_CLOUD_MAX_POOL || sampling->pool % 64 != 0)
+        return fail(LCR_ERR_INVALID, "pool must be a multiple of 64 in 64 .. %d, got %d", LCR_CLOUD_MAX_POOL, sampling->pool);
+    if (sampling->pool < spec->points)
+        return fail(LCR_ERR_INVALID, "pool must be at least points (farthest-point sampling picks %d points out of the pool, which caps points at %d), got %d", spec->points,
+                    LCR_CLOUD_MAX_POOL, sampling->pool);
+    return LCR_OK;
+}
+
+int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) { return lcr_enable_point_cloud_sampled(s, spec, nullptr); }
+
+int lcr_enable_point_cloud_sampled(lcr_sim *s, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_point_cloud_check(spec)) return rc;
+    const lcr_point_cloud_sampling sm = sampling ? *sampling : lcr_point_cloud_sampling{LCR_CLOUD_SAMPLE_STRIDE, 0};
+    if (int rc = lcr_point_cloud_sampling_check(spec, &sm)) return rc;
     SIMCHK(s);
     if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a point cloud of");
     const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
@@ -1666,9 +1691,13 @@ int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) {
     if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
     if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the cloud)");
     if (s->cloud_on) {
-        if (memcmp(&s->cloud_spec, &sp, sizeof sp) == 0) return LCR_OK;
-        return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d) is enabled already and fixed for the life of the handle", s->cloud_spec.points,
-                    s->cloud_spec.cameras, s->cloud_spec.ids, s->cloud_spec.colors);
+        if (memcmp(&s->cloud_spec, &sp, sizeof sp) == 0 && s->cloud_sampling.mode == sm.mode && s->cloud_sampling.pool == sm.pool) return LCR_OK;
+        if (s->cloud_sampling.mode == LCR_CLOUD_SAMPLE_STRIDE && sm.mode == LCR_CLOUD_SAMPLE_STRIDE)
+            return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d) is enabled already and fixed for the life of the handle", s->cloud_spec.points,
+                        s->cloud_spec.cameras, s->cloud_spec.ids, s->cloud_spec.colors);
+        return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d; sampling %s, pool %d) is enabled already and fixed for the life of the handle: "
+                    "asked for points %d, cameras %u, ids 0x%x, colors %d; sampling %s, pool %d", s->cloud_spec.points, s->cloud_spec.cameras, s->cloud_spec.ids,
+                    s->cloud_spec.colors, cloud_mode_name(s->cloud_sampling.mode), s->cloud_sampling.pool, sp.points, sp.cameras, sp.ids, sp.colors, cloud_mode_name(sm.mode), sm.pool);
     }
     LcrCloud A{};
     auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
@@ -1702,10 +1731,12 @@ int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) {
     int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
     if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
     s->cloud = A;
+    s->cloud_sampling = sm;
+    const auto undo = [s, mem] { (void)hipFree(mem); s->cloud = LcrCloud{}; s->cloud_sampling = lcr_point_cloud_sampling{}; };
     if (!rc) rc = launch_cloud(s, s->dev, s->stream, nullptr);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->cloud = LcrCloud{}; return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); undo(); return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { (void)hipFree(mem); s->cloud = LcrCloud{}; return fail(LCR_ERR_HIP, "making the point cloud failed: %s", hipGetErrorString((hipError_t)rc)); }
+    if (rc) { undo(); return fail(LCR_ERR_HIP, "making the point cloud failed: %s", hipGetErrorString((hipError_t)rc)); }
     s->cloud_mem = mem;
     s->cloud_spec = sp;
     s->cloud_on = true;
@@ -1728,6 +1759,13 @@ int lcr_get_point_cloud(lcr_sim *s, lcr_point_cloud_view *out) {
     out->source = s->cloud.source;
     out->camera_pose = s->cloud.pose;
     out->bytes_per_env = (uint64_t)s->cloud.points * s->cloud.channels * sizeof(float);
+    return LCR_OK;
+}
+
+int lcr_get_point_cloud_sampling(lcr_sim *s, lcr_point_cloud_sampling *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (a joining entry point, as lcr_get_point_cloud is)
+    *out = s->cloud_on ? s->cloud_sampling : lcr_point_cloud_sampling{LCR_CLOUD_SAMPLE_STRIDE, 0};
     return LCR_OK;
 }
 

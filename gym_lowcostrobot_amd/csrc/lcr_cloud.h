@@ -34,7 +34,18 @@ struct LcrCloud {
 
 // bytes of dynamic LDS a workgroup takes: one count byte per 16-pixel group, rounded up to whole segments
 size_t lcr_cloud_lds_bytes(int slots, int pixels);
+// whether the point-cloud kernels are built for these arguments (what both launchers check before they launch)
+bool lcr_cloud_args_ok(const LcrCloud &A);
 // 0, or the hipError_t of the launch; -1: arguments the kernel is not built for (nothing is launched)
 int lcr_launch_point_cloud(const LcrCloud &A, void *stream);
+
+// Farthest-point sampling (lcr_enable_point_cloud_sampled with LCR_CLOUD_SAMPLE_FPS; lcr_cloud_fps.hip): the cloud's arguments and the pool.  A struct of its own: LcrCloud
+// and the kernel arguments of the strided kernels stay as they are.
+struct LcrCloudFps {
+    LcrCloud c;   // c.points = P, the points that go out
+    int pool;     // Q: a multiple of 64, P <= Q <= LCR_CLOUD_MAX_POOL
+};
+// as lcr_launch_point_cloud
+int lcr_launch_point_cloud_fps(const LcrCloudFps &F, void *stream);
 
 #endif

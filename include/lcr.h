@@ -547,7 +547,8 @@ int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
  *               after the observation stack.  Fixed for the life of the handle: the same spec again does nothing, another spec is refused.
  *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, points, the same guard from the first 256-byte boundary at or behind their end (as the
  *               stack has them), then count, source and camera_pose.  Freed by lcr_destroy.
- *   not in it   a crop box, random or farthest-point sampling, normals, a base-frame transform, the cloud of an episode that has ended. */
+ *   not in it   a crop box, random or farthest-point sampling, normals, a base-frame transform, the cloud of an episode that has ended.  (Farthest-point sampling from a
+ *               strided pool is an optional mode of its own: "The point cloud by farthest-point sampling" below.) */
 typedef struct lcr_point_cloud_spec {
     int32_t points;       /* P: a multiple of 64 in 64 .. 8192 */
     uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
@@ -572,6 +573,44 @@ int lcr_point_cloud_check(const lcr_point_cloud_spec *spec);
 int lcr_enable_point_cloud(lcr_sim *sim, const lcr_point_cloud_spec *spec);
 /* The cloud; waits (on the handle's stream) for frames and cloud still being made on the second stream, as every entry point but the step does. */
 int lcr_get_point_cloud(lcr_sim *sim, lcr_point_cloud_view *out);
+
+/* == The point cloud by farthest-point sampling (FPS): an optional sampling mode of the point cloud.  The strided selection above is even in image space, not in 3-D: a
+ * surface near a camera takes most of the points.  PointNet-style encoders and 3-D diffusion policies down-sample with FPS instead; this mode does it on the device, in
+ * the cloud's kernel: FPS of P points out of a POOL of Q candidates, the pool chosen by the strided rule.  Off unless asked for: a handle enabled with
+ * lcr_enable_point_cloud, or with LCR_CLOUD_SAMPLE_STRIDE, launches the strided kernel and produces its bytes.
+ *   pool        Q = `pool`: a multiple of 64 with P <= Q <= LCR_CLOUD_MAX_POOL (4096), which caps P at 4096 under FPS as well.  No default: the caller chooses the cost,
+ *               N P Q distance updates per cloud.  Pool entry i (0 <= i < Q) is candidate ((2 i + 1) M) / (2 Q), the selection rule above with Q in place of P, in
+ *               64 bits.  Its point is the point formula above, evaluated as the strided kernel evaluates it: p = ro + t d by the same fmaf chain, r g b by the stack's
+ *               rule with colors = 1.  If 0 < M < Q, candidates repeat in the pool, as they do in a strided cloud.
+ *   order       greedy.  Every pool entry has a float32 `mind`, initially + inf.  For k = 0 .. P - 1: output point k is the pool entry with the largest mind, ties to the
+ *               LOWEST pool index -- the first point is pool entry 0; the pool is monotone in the candidate number, so among distinct tied candidates the one with the
+ *               lowest source wins.  The chosen entry's mind is set to - 1: it is never chosen again.  Every other entry i with mind[i] >= 0 takes
+ *               mind[i] = min(mind[i], dist(i, chosen)).
+ *   distance    pinned to the bit: dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z, one float32 subtraction each; dist = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) -- one
+ *               rounded multiply, then two fused steps, in that order.  Nothing is re-associated or contracted beyond the two fmaf, denormals are kept.  Only x y z enter
+ *               the distance, colours never do.
+ *   output      points[env][k] and source[env][k], in greedy order: the first k points of the buffer are themselves an FPS of k points from the same pool, so a consumer
+ *               may truncate.  count is M, camera_pose is as above.
+ *   M = 0       the env's points are zeros and its sources - 1, as above.      0 < M < P: after the M distinct candidates the remaining outputs are duplicates at
+ *               distance 0, taken in pool order.
+ *   the rest    invariant, ordering (behind the frame and stack kernels, the look and pose snapshots on the second stream, the join event), guards, memory and life are
+ *               those of the point cloud above, word for word.
+ *   not in it   a crop box (a float32 comparison at the box faces would decide what a candidate is: count and source would stop being exact integer decisions; the
+ *               segmentation ids already drop floor and sky), random sampling, normals, pools beyond 4096, FPS over colours. */
+enum { LCR_CLOUD_SAMPLE_STRIDE = 0, LCR_CLOUD_SAMPLE_FPS = 1 };
+#define LCR_CLOUD_MAX_POOL 4096
+typedef struct lcr_point_cloud_sampling {
+    int32_t mode;         /* LCR_CLOUD_SAMPLE_* */
+    int32_t pool;         /* Q under LCR_CLOUD_SAMPLE_FPS: a multiple of 64, points <= pool <= LCR_CLOUD_MAX_POOL; under LCR_CLOUD_SAMPLE_STRIDE it must be 0 */
+} lcr_point_cloud_sampling;
+/* The checks lcr_enable_point_cloud_sampled makes of `sampling` (against an already checked `spec`) before it looks at the handle, on their own: LCR_OK, or
+ * LCR_ERR_INVALID with the field's name first in the message */
+int lcr_point_cloud_sampling_check(const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling);
+/* lcr_enable_point_cloud with a sampling mode; a NULL sampling is LCR_CLOUD_SAMPLE_STRIDE, and lcr_enable_point_cloud(sim, spec) is this call with NULL.  `spec` is checked
+ * first, then `sampling`, then the handle.  Fixed for the life of the handle: the same spec and the same sampling again do nothing; if either differs the call is refused. */
+int lcr_enable_point_cloud_sampled(lcr_sim *sim, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling_or_null);
+/* The sampling of the handle's cloud (mode LCR_CLOUD_SAMPLE_STRIDE and pool 0 for a strided cloud and for a handle without a cloud); joins as lcr_get_point_cloud does. */
+int lcr_get_point_cloud_sampling(lcr_sim *sim, lcr_point_cloud_sampling *out);
 
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n

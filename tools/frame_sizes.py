@@ -1,5 +1,5 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist] [--cloud[=P]]
+    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist] [--cloud[=P]] [--cloud-fps=P,Q [--launches]]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
@@ -16,6 +16,11 @@ writes per ms; (ii) env-steps/s closed and open loop, without and with the camer
 (i) of a sim with both planes and no cloud (the frame kernel) and of a sim with the cloud (frame kernel and cloud kernel back to back on one stream), the cloud kernel's
 time as the difference of the two, the bytes it reads by the model of DESIGN.md section 3.4 -- one segmentation byte per pixel and camera, and per point the 16 id bytes of
 its group again, one depth float (with colours three bytes more) -- and the TB/s that makes.
+--cloud-fps=P,Q: ONLY the point cloud by farthest-point sampling (VecSim(point_cloud=dict(points=P, sampling="fps", pool=Q)), front + top, arm and cubes, x y z), at 84x84
+and 128x128, two rounds of [without, strided P, FPS P out of Q] in turn: (i) of each, the two cloud kernels' times as differences from the sim without a cloud, the FPS
+kernel's N P Q distance updates at ten VALU lane-operations each per second, and that as a share of the VALU peak of 256 CUs x 4 SIMDs x 32 lanes
+at 2.4 GHz.  With --launches nothing is timed: per size, twelve steps and forty masked no-op resets on a strided and on an FPS handle -- the launches a kernel trace of
+this command is read from.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -29,15 +34,18 @@ from gym_lowcostrobot_amd import VecSim  # noqa: E402
 PLANES = "--planes" in sys.argv
 WRIST = "--wrist" in sys.argv
 CLOUD = [a for a in sys.argv[1:] if a == "--cloud" or a.startswith("--cloud=")]
+CLOUD_FPS = [a for a in sys.argv[1:] if a.startswith("--cloud-fps=")]
+FPS_P, FPS_Q = [int(v) for v in CLOUD_FPS[0].split("=")[1].split(",")] if CLOUD_FPS else (0, 0)
+LAUNCHES = "--launches" in sys.argv
 CLOUD_P = int(CLOUD[0].split("=")[1]) if CLOUD and "=" in CLOUD[0] else 1024
 LOOK = [int(k) for k in sys.argv[sys.argv.index("--look") + 1].split(",")] if "--look" in sys.argv else []
-args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ["--planes", "--look", "--wrist"] + CLOUD and sys.argv[i - 1] != "--look"]
+args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ["--planes", "--look", "--wrist", "--launches"] + CLOUD + CLOUD_FPS and sys.argv[i - 1] != "--look"]
 n = int(args[0]) if len(args) > 0 else 32768
 task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
 SOAK_S, WINDOWS, STEPS = 2.0, 7, 60
 print(f"frame sizes: {task}, {n} envs, default preset, LCR_RENDER_EPW={os.environ.get('LCR_RENDER_EPW', '(by frame size)')}")
-if not WRIST and not CLOUD:
+if not WRIST and not CLOUD and not CLOUD_FPS:
     print(f"{'H x W':>9s} {'frame kernel ms':>16s} {'min':>7s} {'max':>7s} {'GB written':>11s} {'TB/s':>6s} {'closed-loop steps/s':>20s} {'open-loop steps/s':>18s}")
 rows = []
 
@@ -160,6 +168,41 @@ if CLOUD:
                     wr = n * CLOUD_P * (4 * C + 4)
                     print(f"{H:4d}x{W:<4d} round {rnd} frame + cloud kernel       {ms:7.3f} ({wmin:.3f} {wmax:.3f})  cloud kernel (difference) {cl:6.3f} ms = {cl / base:.3f} of the frame kernel  "
                           f"reads {rd / 1e9:6.3f} GB -> {rd / cl / 1e9:5.2f} TB/s read, writes {wr / 1e9:.3f} GB; mean M {mean_m:.0f}", flush=True)
+                sim.free(act)
+                sim.close()
+    sys.exit(0)
+
+if CLOUD_FPS:
+    VALU_PEAK = 256 * 4 * 32 * 2.4e9   # lane-operations per second (MI355X_MICROARCH: 157.3 TFLOP/s of fp32 FMAs = 2 x this)
+    updates = n * FPS_P * FPS_Q
+    kinds = [("frame kernel with planes", None), (f"+ strided cloud, P {FPS_P}", FPS_P), (f"+ FPS cloud, P {FPS_P} of Q {FPS_Q}", dict(points=FPS_P, sampling="fps", pool=FPS_Q))]
+    print(f"the point cloud by farthest-point sampling ({n} envs, P = {FPS_P}, Q = {FPS_Q}, front + top, arm and cubes, x y z)" +
+          ("" if LAUNCHES else f": ms per launch (median of {WINDOWS} windows of ten; min max)"))
+    for H, W in [(84, 84), (128, 128)]:
+        for rnd in ((1,) if LAUNCHES else (1, 2)):
+            base = None
+            for name, cloud in kinds[1:] if LAUNCHES else kinds:
+                sim = VecSim(task, n, observation_mode="both", image_size=(H, W), image_planes=("depth", "segmentation"), **({"point_cloud": cloud} if cloud else {}))
+                act = sim.alloc_actions()
+                for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+                    sim.fill_random_actions(act, 1, t % 8)
+                    sim.step_device(act.ptr)
+                if LAUNCHES:
+                    mask = np.zeros(n, np.uint8)
+                    for _ in range(40):
+                        sim.reset(mask=mask)
+                    sim.sync()
+                    print(f"{H:4d}x{W:<4d} {name}: 12 steps and 40 masked no-op resets; mean M {float(sim.point_cloud_count.numpy().mean()):.0f}", flush=True)
+                else:
+                    ms, wmin, wmax = frame_kernel_ms(sim)
+                    line = f"{H:4d}x{W:<4d} round {rnd} {name:34s} {ms:8.3f} ({wmin:.3f} {wmax:.3f})"
+                    if cloud is None:
+                        base = ms
+                    else:
+                        line += f"  cloud kernel (difference) {ms - base:7.3f} ms; mean M {float(sim.point_cloud_count.numpy().mean()):.0f}"
+                    if isinstance(cloud, dict):
+                        line += f"  {updates / 1e9:.1f} G updates x 10 lane-ops -> {10 * updates / (ms - base) / 1e9:.2f} T lane-ops/s = {100 * 10 * updates / ((ms - base) * 1e-3) / VALU_PEAK:.1f} % of the VALU peak"
+                    print(line, flush=True)
                 sim.free(act)
                 sim.close()
     sys.exit(0)
