@@ -59,6 +59,7 @@ SYMBOLS = [
     "lcr_obs_stack_check", "lcr_enable_obs_stack", "lcr_get_obs_stack",
     "lcr_point_cloud_check", "lcr_enable_point_cloud", "lcr_get_point_cloud",
     "lcr_point_cloud_sampling_check", "lcr_enable_point_cloud_sampled", "lcr_get_point_cloud_sampling",
+    "lcr_point_cloud_crop_check", "lcr_enable_point_cloud_cropped", "lcr_get_point_cloud_crop",
 ]
 
 
@@ -412,6 +413,54 @@ class PointCloudSampling(ctypes.Structure):
         return v, out
 
 
+class PointCloudCrop(ctypes.Structure):
+    """lcr_point_cloud_crop: an axis-aligned box in the world frame; a candidate of the cloud must have its point inside it (include/lcr.h)"""
+    _fields_ = [
+        ("lo", ctypes.c_float * 3),      # x, y, z of the lower corner; -inf: an open side
+        ("hi", ctypes.c_float * 3),      # x, y, z of the upper corner; +inf: an open side
+    ]
+
+    def as_dict(self):
+        """the float32 values in use, as Python floats"""
+        return {"lo": tuple(float(v) for v in self.lo), "hi": tuple(float(v) for v in self.hi)}
+
+    @classmethod
+    def take(cls, v):
+        """(what is left of the point_cloud argument, its PointCloudCrop or None): takes `crop` out of a dict -- ((x0, y0, z0), (x1, y1, z1)), None inside a triple an open
+        side; crop=None, or no crop, is a cloud without a box"""
+        import numpy as np
+
+        if not isinstance(v, dict) or "crop" not in v:
+            return v, None
+        v = dict(v)
+        crop = v.pop("crop")
+        if crop is None:
+            return v, None
+        what = "point_cloud: crop must be ((x0, y0, z0), (x1, y1, z1)), the lower and the upper corner of a box in the world frame (None: an open side)"
+        try:
+            lo, hi = crop
+            lo, hi = list(lo), list(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}, got {crop!r}") from None
+        if isinstance(crop, str) or len(lo) != 3 or len(hi) != 3:
+            raise ValueError(f"{what}, got {crop!r}")
+        out = cls()
+        for name, side, dst, open_side in (("lo", lo, out.lo, -np.inf), ("hi", hi, out.hi, np.inf)):
+            for k, x in enumerate(side):
+                if x is None:
+                    x = open_side
+                if isinstance(x, (bool, np.bool_, str)) or not isinstance(x, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"{what}; {name}[{k}] is {x!r}")
+                x = np.float32(x)   # (the float32 value the kernel compares with)
+                if np.isnan(x):
+                    raise ValueError(f"point_cloud: crop {name}[{k}] is NaN (None or an infinity is an open side)")
+                dst[k] = float(x)
+        for k, axis in enumerate("xyz"):
+            if out.lo[k] > out.hi[k]:
+                raise ValueError(f"point_cloud: crop lo[{k}] > hi[{k}]: the box is empty along {axis} (lo {out.lo[k]!r}, hi {out.hi[k]!r})")
+        return v, out
+
+
 class LcrPointCloudView(ctypes.Structure):
     _fields_ = [
         ("enabled", ctypes.c_int32),
@@ -558,6 +607,9 @@ def load():
     L.lcr_point_cloud_sampling_check.argtypes = [ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling)]
     L.lcr_enable_point_cloud_sampled.argtypes = [vp, ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling)]
     L.lcr_get_point_cloud_sampling.argtypes = [vp, ctypes.POINTER(PointCloudSampling)]
+    L.lcr_point_cloud_crop_check.argtypes = [ctypes.POINTER(PointCloudCrop)]
+    L.lcr_enable_point_cloud_cropped.argtypes = [vp, ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling), ctypes.POINTER(PointCloudCrop)]
+    L.lcr_get_point_cloud_crop.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PointCloudCrop)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

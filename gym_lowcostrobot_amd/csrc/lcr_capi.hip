@@ -19,7 +19,7 @@
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
 namespace {
-thread_local char g_err[512] = "";
+thread_local char g_err[768] = "";   // (the longest message, the refusal of another point cloud, names two specs, samplings and crop boxes)
 
 int fail(int code, const char *fmt, ...) {
     va_list ap;
@@ -182,6 +182,8 @@ struct lcr_sim {
     lcr_point_cloud_spec cloud_spec;   // as enabled, cameras and ids resolved
     LcrCloud cloud;                    // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
     lcr_point_cloud_sampling cloud_sampling;   // stride, or farthest-point sampling from a pool (lcr_enable_point_cloud_sampled): which kernel makes the cloud
+    bool cloud_crop_on;                // a crop box (lcr_enable_point_cloud_cropped): the kernels of lcr_cloud_crop.hip make the cloud
+    lcr_point_cloud_crop cloud_crop;
     void *cloud_mem;
 };
 
@@ -222,6 +224,13 @@ static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     A.front = s->cam_front; A.top = s->cam_top;
     if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
     A.qpos = P.qpos;
+    if (s->cloud_crop_on) {   // (a handle without a crop launches what it launched before there was one)
+        LcrCloudCrop B{};
+        B.c = A;
+        for (int k = 0; k < 3; k++) { B.lo[k] = s->cloud_crop.lo[k]; B.hi[k] = s->cloud_crop.hi[k]; }
+        B.pool = s->cloud_sampling.mode == LCR_CLOUD_SAMPLE_FPS ? s->cloud_sampling.pool : 0;
+        return lcr_launch_point_cloud_crop(B, stream);
+    }
     if (s->cloud_sampling.mode == LCR_CLOUD_SAMPLE_FPS) return lcr_launch_point_cloud_fps(LcrCloudFps{A, s->cloud_sampling.pool}, stream);
     return lcr_launch_point_cloud(A, stream);
 }
@@ -1673,13 +1682,42 @@ int lcr_point_cloud_sampling_check(const lcr_point_cloud_spec *spec, const lcr_p
     return LCR_OK;
 }
 
-int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) { return lcr_enable_point_cloud_sampled(s, spec, nullptr); }
+int lcr_point_cloud_crop_check(const lcr_point_cloud_crop *crop) {
+    if (!crop) return fail(LCR_ERR_INVALID, "crop is NULL");
+    static const char *const axis = "xyz";
+    // (by the bits: this unit is built with -ffast-math, under which x != x is no NaN test)
+    const auto is_nan = [](float v) { uint32_t b; memcpy(&b, &v, sizeof b); return (b & 0x7fffffffu) > 0x7f800000u; };
+    for (int k = 0; k < 3; k++) {
+        if (is_nan(crop->lo[k])) return fail(LCR_ERR_INVALID, "lo[%d] (%c) is NaN: every side of the crop box is finite or an infinity (an open side)", k, axis[k]);
+        if (is_nan(crop->hi[k])) return fail(LCR_ERR_INVALID, "hi[%d] (%c) is NaN: every side of the crop box is finite or an infinity (an open side)", k, axis[k]);
+    }
+    for (int k = 0; k < 3; k++)
+        if (crop->lo[k] > crop->hi[k])
+            return fail(LCR_ERR_INVALID, "lo[%d] > hi[%d]: the crop box is empty along %c (lo %.9g, hi %.9g)", k, k, axis[k], (double)crop->lo[k], (double)crop->hi[k]);
+    return LCR_OK;
+}
+
+int lcr_enable_point_cloud(lcr_sim *s, const lcr_point_cloud_spec *spec) { return lcr_enable_point_cloud_cropped(s, spec, nullptr, nullptr); }
 
 int lcr_enable_point_cloud_sampled(lcr_sim *s, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling) {
+    return lcr_enable_point_cloud_cropped(s, spec, sampling, nullptr);
+}
+
+// "; crop lo (x y z) hi (x y z)" or "; no crop" into buf: how the refusals name a box
+static const char *cloud_crop_text(char (&buf)[200], bool on, const lcr_point_cloud_crop &c) {
+    if (!on) snprintf(buf, sizeof buf, "no crop");
+    else snprintf(buf, sizeof buf, "crop lo (%.9g %.9g %.9g) hi (%.9g %.9g %.9g)", (double)c.lo[0], (double)c.lo[1], (double)c.lo[2], (double)c.hi[0], (double)c.hi[1], (double)c.hi[2]);
+    return buf;
+}
+
+int lcr_enable_point_cloud_cropped(lcr_sim *s, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling, const lcr_point_cloud_crop *crop) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_point_cloud_check(spec)) return rc;
     const lcr_point_cloud_sampling sm = sampling ? *sampling : lcr_point_cloud_sampling{LCR_CLOUD_SAMPLE_STRIDE, 0};
     if (int rc = lcr_point_cloud_sampling_check(spec, &sm)) return rc;
+    if (crop)
+        if (int rc = lcr_point_cloud_crop_check(crop)) return rc;
+    const lcr_point_cloud_crop cr = crop ? *crop : lcr_point_cloud_crop{};
     SIMCHK(s);
     if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a point cloud of");
     const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
@@ -1691,7 +1729,17 @@ int lcr_enable_point_cloud_sampled(lcr_sim *s, const lcr_point_cloud_spec *spec,
     if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
     if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the cloud)");
     if (s->cloud_on) {
-        if (memcmp(&s->cloud_spec, &sp, sizeof sp) == 0 && s->cloud_sampling.mode == sm.mode && s->cloud_sampling.pool == sm.pool) return LCR_OK;
+        // (the boxes compare as float32 values: the comparisons the kernel makes with them are the same then; no side is a NaN)
+        bool same_crop = s->cloud_crop_on == (crop != nullptr);
+        for (int k = 0; k < 3 && same_crop && crop; k++) same_crop = s->cloud_crop.lo[k] == cr.lo[k] && s->cloud_crop.hi[k] == cr.hi[k];
+        if (memcmp(&s->cloud_spec, &sp, sizeof sp) == 0 && s->cloud_sampling.mode == sm.mode && s->cloud_sampling.pool == sm.pool && same_crop) return LCR_OK;
+        if (s->cloud_crop_on || crop) {
+            char was[200], asked[200];
+            return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d; sampling %s, pool %d; %s) is enabled already and fixed for the life of the "
+                        "handle: asked for points %d, cameras %u, ids 0x%x, colors %d; sampling %s, pool %d; %s", s->cloud_spec.points, s->cloud_spec.cameras, s->cloud_spec.ids,
+                        s->cloud_spec.colors, cloud_mode_name(s->cloud_sampling.mode), s->cloud_sampling.pool, cloud_crop_text(was, s->cloud_crop_on, s->cloud_crop), sp.points,
+                        sp.cameras, sp.ids, sp.colors, cloud_mode_name(sm.mode), sm.pool, cloud_crop_text(asked, crop != nullptr, cr));
+        }
         if (s->cloud_sampling.mode == LCR_CLOUD_SAMPLE_STRIDE && sm.mode == LCR_CLOUD_SAMPLE_STRIDE)
             return fail(LCR_ERR_INVALID, "a point cloud (points %d, cameras %u, ids 0x%x, colors %d) is enabled already and fixed for the life of the handle", s->cloud_spec.points,
                         s->cloud_spec.cameras, s->cloud_spec.ids, s->cloud_spec.colors);
@@ -1732,7 +1780,12 @@ int lcr_enable_point_cloud_sampled(lcr_sim *s, const lcr_point_cloud_spec *spec,
     if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
     s->cloud = A;
     s->cloud_sampling = sm;
-    const auto undo = [s, mem] { (void)hipFree(mem); s->cloud = LcrCloud{}; s->cloud_sampling = lcr_point_cloud_sampling{}; };
+    s->cloud_crop_on = crop != nullptr;
+    s->cloud_crop = cr;
+    const auto undo = [s, mem] {
+        (void)hipFree(mem);
+        s->cloud = LcrCloud{}; s->cloud_sampling = lcr_point_cloud_sampling{}; s->cloud_crop_on = false; s->cloud_crop = lcr_point_cloud_crop{};
+    };
     if (!rc) rc = launch_cloud(s, s->dev, s->stream, nullptr);
     if (rc < 0) { (void)hipStreamSynchronize(s->stream); undo(); return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
@@ -1766,6 +1819,15 @@ int lcr_get_point_cloud_sampling(lcr_sim *s, lcr_point_cloud_sampling *out) {
     if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
     SIMCHK(s);   // (a joining entry point, as lcr_get_point_cloud is)
     *out = s->cloud_on ? s->cloud_sampling : lcr_point_cloud_sampling{LCR_CLOUD_SAMPLE_STRIDE, 0};
+    return LCR_OK;
+}
+
+int lcr_get_point_cloud_crop(lcr_sim *s, int32_t *enabled, lcr_point_cloud_crop *out) {
+    if (!s || !enabled || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (a joining entry point, as lcr_get_point_cloud is)
+    const bool on = s->cloud_on && s->cloud_crop_on;
+    *enabled = on ? 1 : 0;
+    *out = on ? s->cloud_crop : lcr_point_cloud_crop{};
     return LCR_OK;
 }
 

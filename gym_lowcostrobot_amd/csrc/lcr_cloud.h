@@ -48,4 +48,14 @@ struct LcrCloudFps {
 // as lcr_launch_point_cloud
 int lcr_launch_point_cloud_fps(const LcrCloudFps &F, void *stream);
 
+// The cloud inside a crop box (lcr_enable_point_cloud_cropped with a crop; lcr_cloud_crop.hip): the cloud's arguments, the box and the pool.  A struct of its own, as
+// LcrCloudFps is: LcrCloud and the kernel arguments of the six kernels without a box stay as they are.
+struct LcrCloudCrop {
+    LcrCloud c;             // c.points = P, the points that go out
+    float lo[3], hi[3];     // the box, WORLD frame: lo[k] <= hi[k], each finite or an infinity (an open side), never NaN
+    int pool;               // 0: the strided selection; Q under farthest-point sampling, as LcrCloudFps::pool
+};
+// as lcr_launch_point_cloud
+int lcr_launch_point_cloud_crop(const LcrCloudCrop &B, void *stream);
+
 #endif

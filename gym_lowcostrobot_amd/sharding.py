@@ -65,7 +65,8 @@ class ShardedVecSim:
         # (look_variants / look_sampler too: the sampler is keyed by the global env id, so the shards draw the looks the whole job would)
         # (wrist_camera too: every shard mounts the same camera; shards[i].image_wrist ...)
         # (obs_stack too: every shard keeps the stack of its own envs, shards[i].obs_stack; an env's stack depends on that env alone)
-        # (point_cloud too: every shard keeps the cloud of its own envs, shards[i].point_cloud; an env's cloud depends on that env alone)
+        # (point_cloud too: every shard keeps the cloud of its own envs, shards[i].point_cloud; an env's cloud depends on that env alone.  Its crop box is in the world
+        #  frame, which every env shares: every shard gets the same box, shards[i].point_cloud_crop)
         # (image_planes / depth_far, like every other keyword, go to each shard's VecSim: the planes are per-shard device arrays, shards[i].depth_front ...)
         # every shard declares the whole job (lcr_config.global_envs): the same kernel family on every shard, and lcr_create checks that the cut is at wave boundaries
         kw.setdefault("global_envs", n_envs_total)

@@ -143,11 +143,13 @@ class VecSim:
                 raise ValueError("obs_stack: cameras selects 'wrist', but no wrist_camera is given")
             check(self.L.lcr_obs_stack_check(ctypes.byref(obs_stack)))
         # the point cloud (lcr_enable_point_cloud): None = none, an int = that many points of every camera (arm and cubes, x y z), or a dict of points / cameras / ids / colors
-        # and, for farthest-point sampling from a strided pool (lcr_enable_point_cloud_sampled), sampling="fps" and pool=Q.
+        # and, for farthest-point sampling from a strided pool (lcr_enable_point_cloud_sampled), sampling="fps" and pool=Q; and, for a workspace crop box in the world frame
+        # (lcr_enable_point_cloud_cropped), crop=((x0, y0, z0), (x1, y1, z1)) with None for an open side.
         # Checked here and by the library without a handle (lcr_point_cloud_check), before it is asked for a device.  It is made of both planes: they are not switched on silently
         if point_cloud is not None:
             if observation_mode == "state":
                 raise ValueError("point_cloud needs image observations: observation_mode 'image' or 'both'")
+            point_cloud, cloud_crop = _capi.PointCloudCrop.take(point_cloud)           # (`crop`: None without one)
             point_cloud, cloud_sampling = _capi.PointCloudSampling.take(point_cloud)   # (`sampling` and `pool`: the spec keeps its four fields)
             point_cloud = _capi.PointCloudSpec.from_any(point_cloud)
             if point_cloud.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
@@ -158,6 +160,8 @@ class VecSim:
             if cloud_sampling.mode == _capi.CLOUD_SAMPLINGS["fps"] and cloud_sampling.pool < point_cloud.points:
                 raise ValueError(f"point_cloud: pool must be at least points ({point_cloud.points}), got {cloud_sampling.pool}")
             check(self.L.lcr_point_cloud_sampling_check(ctypes.byref(point_cloud), ctypes.byref(cloud_sampling)))
+            if cloud_crop is not None:
+                check(self.L.lcr_point_cloud_crop_check(ctypes.byref(cloud_crop)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -308,17 +312,24 @@ class VecSim:
             self.obs_stack = DeviceArray(self, sv.data, (N, int(sv.spec.frames), int(sv.channels)) + self.image_size, np.dtype(self.obs_stack_spec["dtype"]))
         self.point_cloud = self.point_cloud_count = self.point_cloud_source = self.point_cloud_pose = self.point_cloud_spec = None
         self.point_cloud_sampling = None   # {"mode": "stride" | "fps", "pool": Q or 0} with a cloud
+        self.point_cloud_crop = None       # {"lo": (x, y, z), "hi": (x, y, z)}, the float32 values in use, with a cloud inside a crop box
         if point_cloud is not None:   # (behind look, wrist camera and planes; before or after the stack)
             try:
-                check(self.L.lcr_enable_point_cloud_sampled(self.handle, ctypes.byref(point_cloud), ctypes.byref(cloud_sampling)))   # (stride: lcr_enable_point_cloud)
+                if cloud_crop is None:
+                    check(self.L.lcr_enable_point_cloud_sampled(self.handle, ctypes.byref(point_cloud), ctypes.byref(cloud_sampling)))   # (stride: lcr_enable_point_cloud)
+                else:
+                    check(self.L.lcr_enable_point_cloud_cropped(self.handle, ctypes.byref(point_cloud), ctypes.byref(cloud_sampling), ctypes.byref(cloud_crop)))
                 cv = _capi.LcrPointCloudView()
                 check(self.L.lcr_get_point_cloud(self.handle, ctypes.byref(cv)))
                 check(self.L.lcr_get_point_cloud_sampling(self.handle, ctypes.byref(cloud_sampling)))
+                crop_on, crop_got = ctypes.c_int32(0), _capi.PointCloudCrop()
+                check(self.L.lcr_get_point_cloud_crop(self.handle, ctypes.byref(crop_on), ctypes.byref(crop_got)))
             except Exception:
                 self.close()
                 raise
             self.point_cloud_spec = cv.spec.as_dict()
             self.point_cloud_sampling = cloud_sampling.as_dict()
+            self.point_cloud_crop = crop_got.as_dict() if crop_on.value else None
             P = int(cv.spec.points)
             self.point_cloud = DeviceArray(self, cv.points, (N, P, int(cv.channels)), np.float32)
             self.point_cloud_count = DeviceArray(self, cv.count, (N,), np.int32)

@@ -547,8 +547,8 @@ int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
  *               after the observation stack.  Fixed for the life of the handle: the same spec again does nothing, another spec is refused.
  *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, points, the same guard from the first 256-byte boundary at or behind their end (as the
  *               stack has them), then count, source and camera_pose.  Freed by lcr_destroy.
- *   not in it   a crop box, random or farthest-point sampling, normals, a base-frame transform, the cloud of an episode that has ended.  (Farthest-point sampling from a
- *               strided pool is an optional mode of its own: "The point cloud by farthest-point sampling" below.) */
+ *   not in it   random sampling, normals, a base-frame transform, the cloud of an episode that has ended.  (Farthest-point sampling from a strided pool and a crop box
+ *               are optional modes of their own: "The point cloud by farthest-point sampling" and "The point cloud inside a crop box" below.) */
 typedef struct lcr_point_cloud_spec {
     int32_t points;       /* P: a multiple of 64 in 64 .. 8192 */
     uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
@@ -595,8 +595,9 @@ int lcr_get_point_cloud(lcr_sim *sim, lcr_point_cloud_view *out);
  *               distance 0, taken in pool order.
  *   the rest    invariant, ordering (behind the frame and stack kernels, the look and pose snapshots on the second stream, the join event), guards, memory and life are
  *               those of the point cloud above, word for word.
- *   not in it   a crop box (a float32 comparison at the box faces would decide what a candidate is: count and source would stop being exact integer decisions; the
- *               segmentation ids already drop floor and sky), random sampling, normals, pools beyond 4096, FPS over colours. */
+ *   not in it   random sampling, normals, pools beyond 4096, FPS over colours.  (A crop box was left out of this mode at first: a float32 comparison at the box faces
+ *               decides what a candidate is, so count and source are exact decisions only if the point itself is pinned to the bit, as the distance above is.  "The
+ *               point cloud inside a crop box" below does that; it combines with this mode.) */
 enum { LCR_CLOUD_SAMPLE_STRIDE = 0, LCR_CLOUD_SAMPLE_FPS = 1 };
 #define LCR_CLOUD_MAX_POOL 4096
 typedef struct lcr_point_cloud_sampling {
@@ -611,6 +612,43 @@ int lcr_point_cloud_sampling_check(const lcr_point_cloud_spec *spec, const lcr_p
 int lcr_enable_point_cloud_sampled(lcr_sim *sim, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling_or_null);
 /* The sampling of the handle's cloud (mode LCR_CLOUD_SAMPLE_STRIDE and pool 0 for a strided cloud and for a handle without a cloud); joins as lcr_get_point_cloud does. */
 int lcr_get_point_cloud_sampling(lcr_sim *sim, lcr_point_cloud_sampling *out);
+
+/* == The point cloud inside a crop box: an optional axis-aligned box in the WORLD frame, lo[3] and hi[3], float32.  The selection to a fixed P (the strided rule) or to a
+ * pool of Q (FPS) happens inside the cloud's kernel: a point outside the workspace has taken a slot that a workspace point should have had, and no consumer can give it
+ * back.  PointNet-style encoders and 3-D diffusion policies crop to the workspace first and down-sample second; this mode does the same, on the device, in the cloud's
+ * kernel.  Off unless asked for: a handle enabled without a crop launches the kernels it launched before, and produces their bytes.
+ *   candidates  a pixel is a candidate if it is one by the id rule of the point cloud above AND its point, below, lies inside the box.  Candidates are numbered as there
+ *               (camera slot, then row-major pixel).  M, count, the strided selection ((2 j + 1) M) / (2 P), the FPS pool ((2 i + 1) M) / (2 Q), source, the M = 0 and
+ *               0 < M < P rules, camera_pose, colours, guards, memory, ordering (the second stream and its snapshots, the join event), invariant and life are those of the
+ *               two sections above, word for word, with "candidate" meaning this.
+ *   point       pinned to the bit in this mode.  Of the pixel (row, px) of a W x H frame, t its float32 depth plane value, ro, X, Y, Z, s the float32 values written to
+ *               camera_pose:  hx = (float)px + 0.5f - 0.5f * (float)W, an exact half-integer;  sx = hx * s, one rounded float32 multiply;
+ *               hy = (float)row + 0.5f - 0.5f * (float)H;  sy = - (hy * s);  and per axis k = x, y, z:  d_k = fmaf(sx, X_k, fmaf(sy, Y_k, - Z_k)),
+ *               p_k = fmaf(t, d_k, ro_k).  This is the expression of the point cloud above; here nothing is re-associated or contracted beyond the fmaf named, and
+ *               denormals are kept.
+ *   inside      lo_k <= p_k && p_k <= hi_k for all three k: float32 comparisons on those bits.  Both faces belong to the box.
+ *   output      the x y z of a cropped cloud ARE these p_k: every point of an env with M > 0 satisfies the inside test exactly.  Under FPS the pool points, and so the
+ *               points that go out, are these bits too; the distance rule is unchanged.  count, source and, in this mode, x y z are reproducible decisions: a model that
+ *               evaluates the chain above with an exact fused multiply-add gets the same bits.
+ *   the box     each of the six numbers is finite or an infinity: lo_k = - inf or hi_k = + inf is an open side.  NaN is refused; lo_k > hi_k is refused, naming the axis;
+ *               lo_k == hi_k is allowed (it usually gives M = 0).  One box per handle, fixed for its life, like spec and sampling.
+ *   depth_far   a surface beyond depth_far sits at depth_far along its ray, as above, and the box then drops it.
+ *   not in it   oriented or per-env boxes, several boxes, a base-frame transform, normals, random sampling. */
+typedef struct lcr_point_cloud_crop {
+    float lo[3];          /* x, y, z of the lower corner, world frame; - inf: open */
+    float hi[3];          /* x, y, z of the upper corner; + inf: open */
+} lcr_point_cloud_crop;
+/* The checks lcr_enable_point_cloud_cropped makes of `crop` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field and the axis in the
+ * message */
+int lcr_point_cloud_crop_check(const lcr_point_cloud_crop *crop);
+/* lcr_enable_point_cloud_sampled with a crop box; a NULL crop is no box, and lcr_enable_point_cloud_sampled(sim, spec, sampling) is this call with a NULL crop.  `spec` is
+ * checked first, then `sampling`, then `crop`, then the handle.  Fixed for the life of the handle: the same spec, sampling and crop again do nothing; if any differs -- a box
+ * on a handle enabled without one and the reverse included -- the call is refused, and the message names what is enabled and what was asked for, boxes included. */
+int lcr_enable_point_cloud_cropped(lcr_sim *sim, const lcr_point_cloud_spec *spec, const lcr_point_cloud_sampling *sampling_or_null,
+                                   const lcr_point_cloud_crop *crop_or_null);
+/* The crop box of the handle's cloud: *enabled = 1 and the box in use, or *enabled = 0 and zeros for a cloud without a box and for a handle without a cloud; joins as
+ * lcr_get_point_cloud does. */
+int lcr_get_point_cloud_crop(lcr_sim *sim, int32_t *enabled, lcr_point_cloud_crop *out);
 
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n

@@ -1,5 +1,5 @@
 """Image observations at several frame sizes: what the frame kernel and a whole step cost at each.
-    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist] [--cloud[=P]] [--cloud-fps=P,Q [--launches]]
+    python tools/frame_sizes.py [n_envs] [task] [--planes] [--look K[,K...]] [--wrist] [--cloud[=P]] [--cloud-fps=P,Q [--launches]] [--cloud-crop=x0,y0,z0,x1,y1,z1]
 For (H, W) in 240x320, 128x128, 84x84, 64x64, default preset, observation_mode "both":
   (i)  the frame kernel alone -- a masked no-op reset re-renders all frames and runs nothing else (tools/render_clocks.py) -- in windows of ten launches after a soak of
        back-to-back launches, timed with device events: median ms, bytes written per launch, TB/s;
@@ -21,6 +21,9 @@ and 128x128, two rounds of [without, strided P, FPS P out of Q] in turn: (i) of 
 kernel's N P Q distance updates at ten VALU lane-operations each per second, and that as a share of the VALU peak of 256 CUs x 4 SIMDs x 32 lanes
 at 2.4 GHz.  With --launches nothing is timed: per size, twelve steps and forty masked no-op resets on a strided and on an FPS handle -- the launches a kernel trace of
 this command is read from.
+--cloud-crop=x0,y0,z0,x1,y1,z1 (with --cloud[=P], --cloud-fps=P,Q or both; inf and -inf are open sides): ONLY the cloud inside that crop box of the world frame beside the
+cloud without one, at 84x84 and 128x128 -- per mode a handle without a box and one with it, and (i) of each with the cloud kernel's time as the difference from the sim
+without a cloud, and the mean M of both: what the box removed.  With --launches nothing is timed, as above: twelve steps and forty masked no-op resets per handle.
 LCR_RENDER_EPW=1|2|4 in the environment pins the frame kernel's envs-per-workgroup mapping for the small sizes (A/B of the mappings; default: chosen by frame size)."""
 import os
 import sys
@@ -35,11 +38,13 @@ PLANES = "--planes" in sys.argv
 WRIST = "--wrist" in sys.argv
 CLOUD = [a for a in sys.argv[1:] if a == "--cloud" or a.startswith("--cloud=")]
 CLOUD_FPS = [a for a in sys.argv[1:] if a.startswith("--cloud-fps=")]
+CLOUD_CROP = [a for a in sys.argv[1:] if a.startswith("--cloud-crop=")]
+CROP = [float(v) for v in CLOUD_CROP[0].split("=")[1].split(",")] if CLOUD_CROP else []
 FPS_P, FPS_Q = [int(v) for v in CLOUD_FPS[0].split("=")[1].split(",")] if CLOUD_FPS else (0, 0)
 LAUNCHES = "--launches" in sys.argv
 CLOUD_P = int(CLOUD[0].split("=")[1]) if CLOUD and "=" in CLOUD[0] else 1024
 LOOK = [int(k) for k in sys.argv[sys.argv.index("--look") + 1].split(",")] if "--look" in sys.argv else []
-args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ["--planes", "--look", "--wrist", "--launches"] + CLOUD + CLOUD_FPS and sys.argv[i - 1] != "--look"]
+args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ["--planes", "--look", "--wrist", "--launches"] + CLOUD + CLOUD_FPS + CLOUD_CROP and sys.argv[i - 1] != "--look"]
 n = int(args[0]) if len(args) > 0 else 32768
 task = args[1] if len(args) > 1 else "stack"
 SIZES = [(240, 320), (128, 128), (84, 84), (64, 64)]
@@ -142,6 +147,44 @@ if WRIST:
                           f"{nb / 2 / wr / 1e9:5.2f} TB/s   steps/s {closed:.3e} / {opened:.3e}", flush=True)
                 for a in act:
                     sim.free(a)
+                sim.close()
+    sys.exit(0)
+
+if CLOUD_CROP:
+    assert len(CROP) == 6 and (CLOUD or CLOUD_FPS), "--cloud-crop takes six numbers and goes with --cloud[=P] and / or --cloud-fps=P,Q"
+    box = (tuple(CROP[:3]), tuple(CROP[3:]))
+    kinds = [("frame kernel with planes", None)]
+    if CLOUD:
+        kinds += [(f"+ strided cloud, P {CLOUD_P}", dict(points=CLOUD_P)), (f"+ strided cloud, P {CLOUD_P}, cropped", dict(points=CLOUD_P, crop=box))]
+    if CLOUD_FPS:
+        fps = dict(points=FPS_P, sampling="fps", pool=FPS_Q)
+        kinds += [(f"+ FPS cloud, P {FPS_P} of Q {FPS_Q}", fps), (f"+ FPS cloud, P {FPS_P} of Q {FPS_Q}, cropped", dict(fps, crop=box))]
+    print(f"the point cloud inside the crop box {box[0]} .. {box[1]} beside the cloud without one ({n} envs, front + top, arm and cubes, x y z)" +
+          ("" if LAUNCHES else f": ms per launch (median of {WINDOWS} windows of ten; min max)"))
+    for H, W in [(84, 84), (128, 128)]:
+        for rnd in ((1,) if LAUNCHES else (1, 2)):
+            base = None
+            for name, cloud in kinds[1:] if LAUNCHES else kinds:
+                sim = VecSim(task, n, observation_mode="both", image_size=(H, W), image_planes=("depth", "segmentation"), **({"point_cloud": cloud} if cloud else {}))
+                act = sim.alloc_actions()
+                for t in range(12):   # (the same twelve steps: the same poses under the cameras)
+                    sim.fill_random_actions(act, 1, t % 8)
+                    sim.step_device(act.ptr)
+                if LAUNCHES:
+                    mask = np.zeros(n, np.uint8)
+                    for _ in range(40):
+                        sim.reset(mask=mask)
+                    sim.sync()
+                    print(f"{H:4d}x{W:<4d} {name}: 12 steps and 40 masked no-op resets; mean M {float(sim.point_cloud_count.numpy().mean()):.0f}", flush=True)
+                else:
+                    ms, wmin, wmax = frame_kernel_ms(sim)
+                    line = f"{H:4d}x{W:<4d} round {rnd} {name:44s} {ms:8.3f} ({wmin:.3f} {wmax:.3f})"
+                    if cloud is None:
+                        base = ms
+                    else:
+                        line += f"  cloud kernel (difference) {ms - base:7.3f} ms; mean M {float(sim.point_cloud_count.numpy().mean()):.0f}"
+                    print(line, flush=True)
+                sim.free(act)
                 sim.close()
     sys.exit(0)
 
