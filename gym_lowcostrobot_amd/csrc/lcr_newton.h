@@ -243,10 +243,35 @@ DEV int newton_solve(NewtonCtx<NC, NRW, WALLS, NCC> &C, float (&y)[6], f3 (&ca)[
             lim_aref[j] = -B_DEF * (lower ? 1.f : -1.f) * C.qd[j] - K_DEF * imp * pos;
         }
     }
-    auto lim_row = [&](int j, float (&g6)[6]) {
+    // ... and, in the one-cube kernels, the rows themselves, L^-1 (+-e_j) of the joints in lim_wave: one forward substitution per joint and SOLVE instead of one in
+    // `dots` and one in `assemble` of every iteration (entries k < j are zero and take no register).  The same operations on the same inputs: the bits stay.  These
+    // kernels spill already, and a value kept across the iterations pays off only where it saves far more instructions than it takes registers -- this one does
+    // (tools/quick_times.py, same box: ReachCube 65 536 envs 1.727 -> 1.701 ms, PushCube 2.287 -> 2.256, PickPlace-ee 2.075 -> 2.013, PushCubeLoop 4.903 -> 4.807); the reciprocals of blk_eval, the
+    // friction sums S_s of the arm slots and the line search's sum m2 jd^2 kept the same way each cost time, and StackTwoCubes gains nothing from the rows
+    // (5.816 -> 5.797 ms, within its noise): its kernels compute them where they are used, as before.  DESIGN section 0c, profiles/r08_newton_consts.txt
+    constexpr bool LIM_ONCE = NC == 1;
+    float glim[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) glim[j][k] = 0.f;
+    }
+    auto lim_row_of = [&](int j, float (&g6)[6]) {
 #pragma unroll
         for (int k = 0; k < 6; k++) g6[k] = k == j ? (C.q[j] < JLO[j] ? 1.f : -1.f) : 0.f;
         fsub(C.CL, g6);
+    };
+    if (LIM_ONCE && wave_lim) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            if ((C.lim_wave >> j) & 1u) lim_row_of(j, glim[j]);
+        }
+    }
+    auto lim_row = [&](int j, float (&g6)[6]) {
+        if constexpr (LIM_ONCE) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) g6[k] = glim[j][k];
+        } else lim_row_of(j, g6);
     };
     // squared friction coefficients of an arm slot's rows (finger geoms: 1.5 / 0.005 / 1e-4; a finger on a cube: max rule; a link proxy: floor 1 and no torsion
     // row -- condim 3 --, on a cube the cube's coefficients)
