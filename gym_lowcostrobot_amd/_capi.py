@@ -60,6 +60,7 @@ SYMBOLS = [
     "lcr_point_cloud_check", "lcr_enable_point_cloud", "lcr_get_point_cloud",
     "lcr_point_cloud_sampling_check", "lcr_enable_point_cloud_sampled", "lcr_get_point_cloud_sampling",
     "lcr_point_cloud_crop_check", "lcr_enable_point_cloud_cropped", "lcr_get_point_cloud_crop",
+    "lcr_enable_obs_stack_terminal", "lcr_get_obs_stack_terminal", "lcr_obs_stack_terminal", "lcr_point_cloud_terminal",
 ]
 
 
@@ -308,6 +309,20 @@ class ObsStackSpec(ctypes.Structure):
         if v:
             raise ValueError(f"unknown obs_stack fields {sorted(v)}")
         return out
+
+
+def take_terminal(v, what):
+    """(what is left of the obs_stack / point_cloud argument `what`, its `terminal` flag): takes `terminal` out of a dict -- a bool, default False: the caller wants the
+    stacks / clouds of episodes that end (VecSim.obs_stack_terminal / point_cloud_terminal, and the keys the vector adapters add); anything else has none"""
+    import numpy as np
+
+    if not isinstance(v, dict) or "terminal" not in v:
+        return v, False
+    v = dict(v)
+    terminal = v.pop("terminal")
+    if not isinstance(terminal, (bool, np.bool_)):
+        raise ValueError(f"{what}: terminal must be a bool, got {terminal!r}")
+    return v, bool(terminal)
 
 
 class LcrObsStackView(ctypes.Structure):
@@ -610,6 +625,10 @@ def load():
     L.lcr_point_cloud_crop_check.argtypes = [ctypes.POINTER(PointCloudCrop)]
     L.lcr_enable_point_cloud_cropped.argtypes = [vp, ctypes.POINTER(PointCloudSpec), ctypes.POINTER(PointCloudSampling), ctypes.POINTER(PointCloudCrop)]
     L.lcr_get_point_cloud_crop.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(PointCloudCrop)]
+    L.lcr_enable_obs_stack_terminal.argtypes = [vp, ctypes.POINTER(ObsStackSpec), i32]
+    L.lcr_get_obs_stack_terminal.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(u64)]
+    L.lcr_obs_stack_terminal.argtypes = [vp, vp, ctypes.c_int, vp]
+    L.lcr_point_cloud_terminal.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

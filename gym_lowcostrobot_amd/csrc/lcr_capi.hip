@@ -177,6 +177,10 @@ struct lcr_sim {
     void *stack_mem;
     size_t stack_bytes_per_env;
     unsigned char *snap_reset[2];      // beside snap_qpos / snap_target / snap_look
+    // terminal stacks (lcr_enable_obs_stack_terminal with keep_terminal = 1): the history [N][K - 1][C][H][W] lies in stack_mem behind the stack's second guard, with a guard
+    // of its own behind it; stack.history is null without it (K = 1 keeps nothing: the terminal stack is the terminal frame)
+    bool stack_keep;
+    size_t stack_hist_bytes_per_env;
     // the point cloud (lcr_enable_point_cloud): one allocation -- guard, points, guard, count, source, camera poses --, fixed for the life of the handle
     bool cloud_on;
     lcr_point_cloud_spec cloud_spec;   // as enabled, cameras and ids resolved
@@ -210,17 +214,21 @@ static int launch_frames(lcr_sim *s, const LcrDev &P, hipStream_t stream, const 
     return rc;
 }
 
-// the stack kernel, behind the frame kernels on their stream: envs with flags[e] != 0 are refilled, `op` (LCR_STACK_*) is what happens to the others (flags null: to all)
-static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *flags, int op) {
+// the stack kernel, behind the frame kernels on their stream: envs with flags[e] != 0 are refilled, `op` (LCR_STACK_*) is what happens to the others (flags null: to all).
+// `step`: the launch of lcr_step, whose flags are did_reset -- on a handle that keeps terminal stacks the refilled envs first save their history (a handle that does
+// not launches the kernel it always has)
+static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *flags, int op, bool step) {
     LcrStack A = s->stack;
     A.flags = flags; A.op = op;
+    A.mode = step && A.history ? LCR_STACK_MODE_SAVE : LCR_STACK_MODE_PLAIN;
     return lcr_launch_obs_stack(A, stream);
 }
 
 // the cloud kernel, behind the frame kernels (and the stack kernel) on their stream: the cloud of P's envs from the frames just drawn, with the cameras that drew them --
 // the handle's or, with a look, those of the envs' variants (`look` as in look_args) -- and the wrist pose from P's qpos, the pose snapshot the wrist frames were drawn from
-static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
-    LcrCloud A = s->cloud;
+// `view` (or null: the handle's own buffers): the cloud's arguments with planes, frames, outputs and n of a view of some envs (lcr_point_cloud_terminal)
+static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const LcrCloud *view = nullptr) {
+    LcrCloud A = view ? *view : s->cloud;
     A.front = s->cam_front; A.top = s->cam_top;
     if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
     A.qpos = P.qpos;
@@ -237,9 +245,9 @@ static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
 
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
 // handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), and on a handle with a point cloud its kernel last
-static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op) {
+static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
-    if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op));
+    if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
     if (s->cloud_on) LAUNCHCHK("point-cloud kernel", launch_cloud(s, P, stream, look));
     return LCR_OK;
 }
@@ -805,11 +813,11 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
         // (the stack before ev_rdone: join_render then covers it as it covers the frames)
-        if (int rc = frames_after(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr, s->snap_reset[p], LCR_STACK_PUSH)) return rc;
+        if (int rc = frames_after(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr, s->snap_reset[p], LCR_STACK_PUSH, true)) return rc;
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
     } else if (s->has_images) {   // same stream as the step kernel: did_reset itself is current until the next step
-        if (int rc = frames_after(s, s->dev, s->stream, nullptr, s->dev.did_reset, LCR_STACK_PUSH)) return rc;
+        if (int rc = frames_after(s, s->dev, s->stream, nullptr, s->dev.did_reset, LCR_STACK_PUSH, true)) return rc;
     }
     return LCR_OK;
 }
@@ -1584,16 +1592,21 @@ int lcr_obs_stack_check(const lcr_obs_stack_spec *spec) {
     return LCR_OK;
 }
 
-int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
-    // the argument first, the handle afterwards (what can be refused without a device is)
+int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) { return lcr_enable_obs_stack_terminal(s, spec, 0); }
+
+int lcr_enable_obs_stack_terminal(lcr_sim *s, const lcr_obs_stack_spec *spec, int32_t keep_terminal) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_obs_stack_check(spec)) return rc;
+    if (keep_terminal != 0 && keep_terminal != 1) return fail(LCR_ERR_INVALID, "keep_terminal must be 0 or 1, got %d", keep_terminal);
     SIMCHK(s);
     if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to stack");
     lcr_obs_stack_spec sp = *spec;
     if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
     if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the stack)");
     if (s->stack_on) {
-        if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0) return LCR_OK;
+        if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0 && s->stack_keep == (keep_terminal == 1)) return LCR_OK;
+        if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0)
+            return fail(LCR_ERR_INVALID, "an observation stack with keep_terminal %d is enabled already and fixed for the life of the handle (asked for keep_terminal %d)", s->stack_keep ? 1 : 0, keep_terminal);
         return fail(LCR_ERR_INVALID, "an observation stack (frames %d, cameras %u, dtype %d, reset_fill %d) is enabled already and fixed for the life of the handle", s->stack_spec.frames,
                     s->stack_spec.cameras, s->stack_spec.dtype, s->stack_spec.reset_fill);
     }
@@ -1608,6 +1621,10 @@ int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
     C.skip(LCR_WRIST_GUARD);
     const size_t o_dst = C.take(N * per_env);
     C.skip(LCR_WRIST_GUARD);
+    // ... with keep_terminal and older slots to keep: the history and a guard behind it (the guard before it is the stack's second)
+    const size_t hist_env = keep_terminal && sp.frames > 1 ? (size_t)(sp.frames - 1) * 3 * A.ncam * px * esize : 0;
+    const size_t o_hist = C.take(N * hist_env);
+    if (hist_env) C.skip(LCR_WRIST_GUARD);
     const size_t guarded = C.off;
     size_t o_snap[2] = {C.off, C.off};
     if (s->rstream) for (int p = 0; p < 2; p++) o_snap[p] = C.take(N);
@@ -1620,8 +1637,11 @@ int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
     A.n = s->dev.n; A.pixels = (int)px; A.frames = sp.frames; A.dtype = sp.dtype;
     A.zero_fill = sp.reset_fill == LCR_STACK_FILL_ZERO;
     A.flags = nullptr; A.op = LCR_STACK_REFILL;
+    A.mode = LCR_STACK_MODE_PLAIN; A.ids = nullptr;
+    A.history = hist_env ? base + o_hist : nullptr;
     int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
     if (!rc && off > guarded) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    if (!rc && hist_env) rc = (int)hipMemsetAsync(base + o_hist, 0, N * hist_env, s->stream);   // (the history alone: the padding behind it belongs to its guard)
     if (!rc) rc = lcr_launch_obs_stack(A, s->stream);
     if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); return fail(LCR_ERR_UNSUPPORTED, "the observation stack of %d envs at %d x %d needs more workgroups than one launch takes", s->dev.n, s->dev.img_w, s->dev.img_h); }
     if (!rc) rc = (int)hipStreamSynchronize(s->stream);
@@ -1630,6 +1650,8 @@ int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) {
     s->stack_mem = mem;
     s->stack_spec = sp;
     s->stack_bytes_per_env = per_env;
+    s->stack_keep = keep_terminal == 1;
+    s->stack_hist_bytes_per_env = hist_env;
     for (int p = 0; p < 2; p++) s->snap_reset[p] = s->rstream ? (unsigned char *)(base + o_snap[p]) : nullptr;
     s->stack_on = true;
     return LCR_OK;
@@ -1648,6 +1670,52 @@ int lcr_get_obs_stack(lcr_sim *s, lcr_obs_stack_view *out) {
     out->data = s->stack.dst;
     out->bytes_per_env = (uint64_t)s->stack_bytes_per_env;
     return LCR_OK;
+}
+
+int lcr_get_obs_stack_terminal(lcr_sim *s, int32_t *keep_terminal, const void **history, uint64_t *history_bytes_per_env) {
+    if (!s || !keep_terminal || !history || !history_bytes_per_env) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (a joining entry point, as lcr_get_obs_stack is: the history is written by the stack kernel, on the second stream after a step)
+    const bool on = s->stack_on && s->stack_keep;
+    *keep_terminal = on ? 1 : 0;
+    *history = on ? s->stack.history : nullptr;
+    *history_bytes_per_env = on ? (uint64_t)s->stack_hist_bytes_per_env : 0;
+    return LCR_OK;
+}
+
+int lcr_obs_stack_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, void *out_host) {
+    SIMCHK(s);
+    if (!s->stack_on) return fail(LCR_ERR_INVALID, "no observation stack is enabled on this sim (lcr_enable_obs_stack_terminal)");
+    if (!s->stack_keep) return fail(LCR_ERR_INVALID, "the observation stack of this sim was enabled without keep_terminal: the history of an episode that ends is not kept (lcr_enable_obs_stack_terminal)");
+    if (count < 0 || (count > 0 && (!env_ids_host || !out_host))) return fail(LCR_ERR_INVALID, "NULL argument");
+    const size_t img = (size_t)s->dev.img_h * s->dev.img_w * 3, env_out = s->stack_bytes_per_env;
+    const bool wrist = s->stack_spec.cameras & LCR_STACK_CAM_WRIST;
+    const size_t per_env[] = {img, img, wrist ? img : 0, env_out};   // the terminal frames of front, top and -- if it is stacked -- wrist, the terminal stacks
+    return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
+        P1.img_front = (unsigned char *)buf[0];
+        P1.img_top = (unsigned char *)buf[1];
+        if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, nullptr, s->stream));
+        else LAUNCHCHK("render", lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream));
+        if (wrist) {
+            LcrWrist W1 = s->wrist;
+            W1.img = (unsigned char *)buf[2];
+            W1.depth = nullptr; W1.seg = nullptr;
+            LAUNCHCHK("render", lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream));
+        }
+        // slots 0 .. K - 2 from the history of the listed envs, slot K - 1 the terminal frames by the stack's transpose and cast
+        LcrStack A = s->stack;
+        A.ncam = 0;
+        if (s->stack_spec.cameras & LCR_STACK_CAM_FRONT) A.src[A.ncam++] = (const unsigned char *)buf[0];
+        if (s->stack_spec.cameras & LCR_STACK_CAM_TOP) A.src[A.ncam++] = (const unsigned char *)buf[1];
+        if (wrist) A.src[A.ncam++] = (const unsigned char *)buf[2];
+        A.dst = buf[3];
+        A.n = c;
+        A.flags = nullptr; A.op = LCR_STACK_NEWEST;
+        A.mode = LCR_STACK_MODE_TERMINAL;
+        A.ids = (const int *)s->term_stage;   // (the ids of this pass lie first in the staging: render_terminal_passes)
+        LAUNCHCHK("stack kernel", lcr_launch_obs_stack(A, s->stream));
+        HIPCHK(hipMemcpyAsync((char *)out_host + done * env_out, buf[3], env_out * c, hipMemcpyDeviceToHost, s->stream));
+        return LCR_OK;
+    });
 }
 
 // ---- the point cloud ----
@@ -1829,6 +1897,55 @@ int lcr_get_point_cloud_crop(lcr_sim *s, int32_t *enabled, lcr_point_cloud_crop 
     *enabled = on ? 1 : 0;
     *out = on ? s->cloud_crop : lcr_point_cloud_crop{};
     return LCR_OK;
+}
+
+int lcr_point_cloud_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, float *points_host, int32_t *count_host, int32_t *source_host, float *pose_host) {
+    SIMCHK(s);
+    if (!s->cloud_on) return fail(LCR_ERR_INVALID, "no point cloud is enabled on this sim (lcr_enable_point_cloud)");
+    if (count < 0 || (count > 0 && !env_ids_host)) return fail(LCR_ERR_INVALID, "NULL argument");
+    const bool wrist = s->cloud_spec.cameras & LCR_STACK_CAM_WRIST;
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, dpx = px * sizeof(float), wi = wrist ? img : 0, wd = wrist ? dpx : 0, ws = wrist ? px : 0;
+    const size_t P = (size_t)s->cloud.points, pts = P * s->cloud.channels * sizeof(float), src = P * sizeof(int), pose = (size_t)s->cloud.slots * 13 * sizeof(float);
+    // front, top of the colours, the depths, the segmentations; the wrist camera's three if it is selected; then what the cloud kernel writes: points, count, source, poses
+    const size_t per_env[] = {img, img, dpx, dpx, px, px, wi, wd, ws, pts, sizeof(int), src, pose};
+    return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
+        P1.img_front = (unsigned char *)buf[0];
+        P1.img_top = (unsigned char *)buf[1];
+        LcrPlanes PL1 = s->pl;
+        PL1.depth_front = (float *)buf[2];
+        PL1.depth_top = (float *)buf[3];
+        PL1.seg_front = (unsigned char *)buf[4];
+        PL1.seg_top = (unsigned char *)buf[5];
+        if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, &PL1, s->stream));
+        else LAUNCHCHK("render", lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream));
+        if (wrist) {
+            LcrWrist W1 = s->wrist;
+            W1.img = (unsigned char *)buf[6];
+            W1.depth = (float *)buf[7];
+            W1.seg = (unsigned char *)buf[8];
+            LAUNCHCHK("render", lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream));
+        }
+        // the handle's own cloud kernel over the view: planes, frames and outputs in the staging, the wrist pose from the gathered terminal poses, the terminal looks
+        LcrCloud A = s->cloud;
+        A.n = c;
+        for (int i = 0; i < A.slots; i++) {
+            const int b = A.cam[i] == LCR_CLOUD_CAM_FRONT ? 0 : A.cam[i] == LCR_CLOUD_CAM_TOP ? 1 : 2;
+            A.rgb[i] = (const unsigned char *)buf[b == 2 ? 6 : b];
+            A.depth[i] = (const float *)buf[b == 2 ? 7 : 2 + b];
+            A.seg[i] = (const unsigned char *)buf[b == 2 ? 8 : 4 + b];
+        }
+        A.out = (float *)buf[9];
+        A.count = (int *)buf[10];
+        A.source = (int *)buf[11];
+        A.pose = (float *)buf[12];   // [slots][13][c]
+        LAUNCHCHK("point-cloud kernel", launch_cloud(s, P1, s->stream, s->look_K ? LK.variant : nullptr, &A));
+        if (points_host) HIPCHK(hipMemcpyAsync((char *)points_host + done * pts, buf[9], pts * c, hipMemcpyDeviceToHost, s->stream));
+        if (count_host) HIPCHK(hipMemcpyAsync(count_host + done, buf[10], sizeof(int) * c, hipMemcpyDeviceToHost, s->stream));
+        if (source_host) HIPCHK(hipMemcpyAsync(source_host + done * P, buf[11], src * c, hipMemcpyDeviceToHost, s->stream));
+        if (pose_host)   // the pass's columns of [slots][13][count]
+            HIPCHK(hipMemcpy2DAsync(pose_host + done, sizeof(float) * count, buf[12], sizeof(float) * c, sizeof(float) * c, (size_t)s->cloud.slots * 13, hipMemcpyDeviceToHost, s->stream));
+        return LCR_OK;
+    });
 }
 
 int lcr_calibrate_copy(lcr_sim *s, float *dst_dev, size_t n_floats) {

@@ -7,6 +7,13 @@
 // what the kernel does with an env.  An env whose flag byte is set is always refilled; `op` is what happens to the others (and to all without flags).
 enum { LCR_STACK_PUSH = 0, LCR_STACK_NEWEST = 1, LCR_STACK_REFILL = 2 };
 
+// which build of the kernel runs (a template parameter: the plain build is the kernel of a handle that keeps no terminal stacks, with nothing added to it).
+//   SAVE      lcr_step on a handle that keeps terminal stacks (op PUSH, flags = did_reset or its snapshot): an env whose flag is set first copies its slots 1 .. K - 1 to
+//             history[env], then is refilled.
+//   TERMINAL  the assembly of lcr_obs_stack_terminal over a view of n listed envs: dst[e] takes slots 0 .. K - 2 from history[ids[e]] and slot K - 1 from src; flags and op
+//             are not looked at.
+enum { LCR_STACK_MODE_PLAIN = 0, LCR_STACK_MODE_SAVE = 1, LCR_STACK_MODE_TERMINAL = 2 };
+
 #define LCR_STACK_TILE 1024   // pixels of one camera of one env a wave takes (the last tile of a frame may hold fewer, a multiple of 16)
 
 struct LcrStack {
@@ -18,6 +25,9 @@ struct LcrStack {
     int dtype;                     // lcr_obs_stack_dtype
     int op;                        // LCR_STACK_*
     int zero_fill;                 // a refill writes zeros (not the new frames) to slots 0 .. K - 2
+    int mode;                      // LCR_STACK_MODE_*
+    void *history;                 // [N][frames - 1][3 ncam][pixels] of the element type (SAVE: written, TERMINAL: read), or null
+    const int *ids;                // TERMINAL: [n] env ids of the view's envs, the rows of `history`
 };
 
 // 0, or the hipError_t of the launch; -1: arguments the kernel is not built for (nothing is launched)

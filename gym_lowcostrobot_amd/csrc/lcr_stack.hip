@@ -13,6 +13,8 @@
 //     odd: the 16 lanes of a ds_read_b128 group or of a ds_read2_b64 access fall on 16 distinct slots / pairs (3 l mod 16), the 32 lanes of a ds_read_b64 or dword-read half on
 //     32 distinct pairs / banks (3 l mod 32): conflict-free without padding or swizzle.
 //     The de-interleave is byte extraction in registers.
+// Terminal stacks (lcr_enable_obs_stack_terminal) are two more builds of the same kernel, chosen by the template parameter MODE (lcr_stack.h): SAVE adds K - 1 vector loads and
+// stores per channel to the refill of an env the step has reset, TERMINAL gathers those vectors back beside the terminal frames.  The mapping above is unchanged in both.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lcr.h"
@@ -49,7 +51,10 @@ __device__ __forceinline__ v4u channel_vec(const unsigned *w, int c) {
     return v4u{o[0], o[1], o[2], o[3]};
 }
 
-template <int DT, int K>
+// MODE (lcr_stack.h): LCR_STACK_MODE_PLAIN is the kernel as it has always been.  LCR_STACK_MODE_SAVE is what lcr_step launches on a handle that keeps terminal stacks: an env
+// whose flag byte is set first copies its slots 1 .. K - 1 to A.history[env] and is then refilled.  LCR_STACK_MODE_TERMINAL assembles terminal stacks over a view of
+// A.n listed envs: slots 0 .. K - 2 come from A.history[A.ids[env]], slot K - 1 from the view's (terminal) frames; the live stack is not touched.
+template <int DT, int K, int MODE>
 __global__ __launch_bounds__(64) void lcr_obs_stack_kernel(const LcrStack A, const unsigned tiles) {
     constexpr int G = DT == LCR_STACK_UINT8 ? 16 : DT == LCR_STACK_FLOAT16 ? 8 : 4;   // pixels of one channel in 16 B
     constexpr int PASSES = LCR_STACK_TILE / (64 * G);
@@ -92,6 +97,41 @@ __global__ __launch_bounds__(64) void lcr_obs_stack_kernel(const LcrStack A, con
         for (int c = 0; c < 3; c++) fresh[c] = channel_vec<DT>(w, c);
 
         v4u *const p = tile0 + g;   // this lane's vector of channel 0 in slot 0; channel c: + c pv, slot j: + j sv
+        if constexpr (MODE == LCR_STACK_MODE_TERMINAL) {
+            if constexpr (K > 1) {
+                // the history of env id holds what its slots 1 .. K - 1 were, at the offsets they had: [K - 1][C][pixels]; read only, and this lane alone writes p + ...
+                const v4u *const h = (const v4u *)A.history + (size_t)A.ids[env] * (K - 1) * sv + (size_t)cam * 3 * pv + (size_t)tile * (LCR_STACK_TILE / G) + g;
+                v4u old[3][K - 1];
+#pragma unroll
+                for (int j = 0; j < K - 1; j++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) old[c][j] = h[c * pv + (size_t)j * sv];
+#pragma unroll
+                for (int j = 0; j < K - 1; j++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) p[c * pv + (size_t)j * sv] = old[c][j];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) p[c * pv + (size_t)(K - 1) * sv] = fresh[c];
+            continue;
+        }
+        if constexpr (MODE == LCR_STACK_MODE_SAVE && K > 1) {
+            if (op == LCR_STACK_REFILL) {
+                // The episode of this env has ended: what its slots 1 .. K - 1 hold goes to the same offsets of history[env] before the refill below overwrites it.  The
+                // ownership argument of the push holds here too -- these offsets of the stack and of the history are this lane's alone -- and every load comes before
+                // every store, of the history and of the refill: nothing to synchronise.
+                v4u *const h = (v4u *)A.history + (size_t)env * (K - 1) * sv + (size_t)cam * 3 * pv + (size_t)tile * (LCR_STACK_TILE / G) + g;
+                v4u old[3][K - 1];
+#pragma unroll
+                for (int j = 0; j < K - 1; j++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) old[c][j] = p[c * pv + (size_t)(j + 1) * sv];
+#pragma unroll
+                for (int j = 0; j < K - 1; j++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) h[c * pv + (size_t)j * sv] = old[c][j];
+            }
+        }
         if (op == LCR_STACK_PUSH) {
             if constexpr (K > 1) {
                 // In place, without a second buffer: this lane -- and no other lane of any workgroup -- owns the vectors p + c pv + j sv, j = 0 .. K - 1, the SAME offsets
@@ -120,14 +160,21 @@ __global__ __launch_bounds__(64) void lcr_obs_stack_kernel(const LcrStack A, con
     }
 }
 
-template <int DT>
+template <int DT, int MODE>
 void launch_frames_of(const LcrStack &A, unsigned tiles, unsigned blocks, hipStream_t st) {
-#define LCR_STACK_CASE(k) case k: hipLaunchKernelGGL((lcr_obs_stack_kernel<DT, k>), dim3(blocks), dim3(64), 0, st, A, tiles); break
+#define LCR_STACK_CASE(k) case k: hipLaunchKernelGGL((lcr_obs_stack_kernel<DT, k, MODE>), dim3(blocks), dim3(64), 0, st, A, tiles); break
     switch (A.frames) {
         LCR_STACK_CASE(1); LCR_STACK_CASE(2); LCR_STACK_CASE(3); LCR_STACK_CASE(4);
         LCR_STACK_CASE(5); LCR_STACK_CASE(6); LCR_STACK_CASE(7); LCR_STACK_CASE(8);
     }
 #undef LCR_STACK_CASE
+}
+
+template <int MODE>
+void launch_mode_of(const LcrStack &A, unsigned tiles, unsigned blocks, hipStream_t st) {
+    if (A.dtype == LCR_STACK_UINT8) launch_frames_of<LCR_STACK_UINT8, MODE>(A, tiles, blocks, st);
+    else if (A.dtype == LCR_STACK_FLOAT16) launch_frames_of<LCR_STACK_FLOAT16, MODE>(A, tiles, blocks, st);
+    else launch_frames_of<LCR_STACK_FLOAT32, MODE>(A, tiles, blocks, st);
 }
 
 }  // namespace
@@ -141,10 +188,14 @@ int lcr_launch_obs_stack(const LcrStack &A, void *stream) {
     const unsigned tiles = (unsigned)((A.pixels + LCR_STACK_TILE - 1) / LCR_STACK_TILE);
     const unsigned long long blocks = (unsigned long long)A.n * (unsigned)A.ncam * tiles;
     if (blocks > 0x7fffffffull) return -1;
+    // the save needs somewhere to save to and somebody to say who was reset; the assembly the ids of the view's envs and, with older slots, their history
+    if (A.mode != LCR_STACK_MODE_PLAIN && A.mode != LCR_STACK_MODE_SAVE && A.mode != LCR_STACK_MODE_TERMINAL) return -1;
+    if (A.mode == LCR_STACK_MODE_SAVE && (!A.history || !A.flags || A.op != LCR_STACK_PUSH || A.frames < 2)) return -1;
+    if (A.mode == LCR_STACK_MODE_TERMINAL && (!A.ids || (A.frames > 1 && !A.history))) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (A.dtype == LCR_STACK_UINT8) launch_frames_of<LCR_STACK_UINT8>(A, tiles, (unsigned)blocks, st);
-    else if (A.dtype == LCR_STACK_FLOAT16) launch_frames_of<LCR_STACK_FLOAT16>(A, tiles, (unsigned)blocks, st);
-    else launch_frames_of<LCR_STACK_FLOAT32>(A, tiles, (unsigned)blocks, st);
+    if (A.mode == LCR_STACK_MODE_SAVE) launch_mode_of<LCR_STACK_MODE_SAVE>(A, tiles, (unsigned)blocks, st);
+    else if (A.mode == LCR_STACK_MODE_TERMINAL) launch_mode_of<LCR_STACK_MODE_TERMINAL>(A, tiles, (unsigned)blocks, st);
+    else launch_mode_of<LCR_STACK_MODE_PLAIN>(A, tiles, (unsigned)blocks, st);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -67,6 +67,7 @@ class ShardedVecSim:
         # (obs_stack too: every shard keeps the stack of its own envs, shards[i].obs_stack; an env's stack depends on that env alone)
         # (point_cloud too: every shard keeps the cloud of its own envs, shards[i].point_cloud; an env's cloud depends on that env alone.  Its crop box is in the world
         #  frame, which every env shares: every shard gets the same box, shards[i].point_cloud_crop)
+        # (terminal=True in obs_stack / point_cloud too: obs_stack_terminal() / point_cloud_terminal() below take GLOBAL env ids and ask the shard that owns each)
         # (image_planes / depth_far, like every other keyword, go to each shard's VecSim: the planes are per-shard device arrays, shards[i].depth_front ...)
         # every shard declares the whole job (lcr_config.global_envs): the same kernel family on every shard, and lcr_create checks that the cut is at wave boundaries
         kw.setdefault("global_envs", n_envs_total)
@@ -98,6 +99,47 @@ class ShardedVecSim:
 
         ls = [s.look() for s in self.shards]
         return {"variants": ls[0]["variants"], **{k: np.concatenate([l[k] for l in ls], axis=-1) for k in ("variant", "rgb", "episode")}}
+
+    def _by_shard(self, env_ids):
+        """global env ids -> per shard (positions in env_ids, local ids); an id outside the job goes to the nearest shard, whose library refuses it"""
+        import numpy as np
+
+        ids = np.ascontiguousarray(env_ids, np.int64).reshape(-1)
+        owner = np.clip(ids // self.per, 0, len(self.shards) - 1)
+        return ids, [(np.nonzero(owner == g)[0], (ids[owner == g] - g * self.per).astype(np.int32)) for g in range(len(self.shards))]
+
+    def obs_stack_terminal(self, env_ids):
+        """VecSim.obs_stack_terminal over the job's global env ids: every shard makes the terminal stacks of its own envs, in the order of env_ids"""
+        import numpy as np
+
+        ids, parts = self._by_shard(env_ids)
+        s0 = self.shards[0]
+        if s0.obs_stack is None:
+            raise ValueError("obs_stack_terminal: no obs_stack is enabled")
+        out = np.empty((ids.size,) + s0.obs_stack.shape[1:], s0.obs_stack.dtype)
+        for s, (pos, local) in zip(self.shards, parts):
+            if pos.size:
+                out[pos] = s.obs_stack_terminal(local)
+        return out
+
+    def point_cloud_terminal(self, env_ids):
+        """VecSim.point_cloud_terminal over the job's global env ids, in the order of env_ids (pose: (slots, 13, len(env_ids)))"""
+        import numpy as np
+
+        ids, parts = self._by_shard(env_ids)
+        s0 = self.shards[0]
+        if s0.point_cloud is None:
+            raise ValueError("point_cloud_terminal: no point_cloud is enabled")
+        n = ids.size
+        out = {"point_cloud": np.empty((n,) + s0.point_cloud.shape[1:], np.float32), "count": np.empty(n, np.int32),
+               "source": np.empty((n,) + s0.point_cloud_source.shape[1:], np.int32), "pose": np.empty(s0.point_cloud_pose.shape[:2] + (n,), np.float32)}
+        for s, (pos, local) in zip(self.shards, parts):
+            if pos.size:
+                got = s.point_cloud_terminal(local)
+                for k in ("point_cloud", "count", "source"):
+                    out[k][pos] = got[k]
+                out["pose"][:, :, pos] = got["pose"]
+        return out
 
     def outputs(self):
         import numpy as np

@@ -57,6 +57,13 @@ def _obs_spaces(sim, observation_mode):
             subs["image_wrist"] = sp.Box(0, 255, shape=sim.image_size + (3,), dtype=np.uint8)
         for k in sim.plane_arrays():   # VecSim(image_planes=...): depth_front / depth_top in metres up to depth_far, segmentation_front / segmentation_top ids (include/lcr.h)
             subs[k] = sp.Box(0.0, sim.depth_far, shape=sim.image_size, dtype=np.float32) if k.startswith("depth_") else sp.Box(0, 255, shape=sim.image_size, dtype=np.uint8)
+        # VecSim(obs_stack=dict(..., terminal=True)) / (point_cloud=dict(..., terminal=True)): the stack (K, C, H, W) of its element type and the cloud (P, C), for which
+        # the library can make the terminal observation as well.  Without terminal=True neither is exposed (count, source and pose of the cloud are no observations)
+        if sim.obs_stack is not None and sim.obs_stack_keeps_terminal:
+            dt = sim.obs_stack.dtype
+            subs["obs_stack"] = sp.Box(0, 255, shape=sim.obs_stack.shape[1:], dtype=np.uint8) if dt == np.uint8 else sp.Box(0.0, 1.0, shape=sim.obs_stack.shape[1:], dtype=dt.type)
+        if sim.point_cloud is not None and sim.point_cloud_wants_terminal:
+            subs["point_cloud"] = sp.Box(-np.inf, np.inf, shape=sim.point_cloud.shape[1:], dtype=np.float32)
     if observation_mode in ("state", "both"):
         subs[sim.cube_name] = sp.Box(-10.0, 10.0, shape=(3,), dtype=np.float32)
         if sim.task_name == "stack":
@@ -68,7 +75,8 @@ class LowCostRobotVecEnv(_SB3VecEnv):
     def __init__(self, task, num_envs, seed=0, device=0, env_id_offset=0, **kw):
         kw.setdefault("observation_mode", "state")
         self.observation_mode = kw["observation_mode"]
-        if kw.get("point_cloud") is not None:   # (as the observation stack)
+        pc = kw.get("point_cloud")
+        if pc is not None and not (isinstance(pc, dict) and pc.get("terminal", False) is not False):   # (with terminal=True the cloud is exposed, terminal observation included; VecSim checks the value)
             raise ValueError("point_cloud is for on-device loops over VecSim: an env the step has auto-reset shows its reset state, so the cloud of the episode that ended is gone, "
                              "and LowCostRobotVecEnv / LowCostRobotVectorEnv, which owe SB3 / gymnasium a complete terminal_observation, do not expose it")
         self.sim = VecSim(task, num_envs, device=device, env_id_offset=env_id_offset, base_seed=seed, auto_reset=True, **kw)
@@ -100,10 +108,14 @@ class LowCostRobotVecEnv(_SB3VecEnv):
                 o["image_wrist"] = sim.image_wrist.numpy()
             for k, a in sim.plane_arrays().items():
                 o[k] = a.numpy()
+            if "obs_stack" in self._keys:
+                o["obs_stack"] = sim.obs_stack.numpy()
+            if "point_cloud" in self._keys:
+                o["point_cloud"] = sim.point_cloud.numpy()
         # forced copies: the pinned mirror is overwritten by the next fetch and freed by close(), and SB3 keeps the returned arrays
         # in its rollout buffer (np.ascontiguousarray would hand out a VIEW of the mirror when num_envs == 1, where the transposed
         # (6, 1) view already counts as contiguous); the frames come from a device-to-host copy of their own
-        return {k: (o[k] if k.startswith(("image_", "depth_", "segmentation_")) else np.array(o[k], copy=True, order="C")) for k in self._keys}
+        return {k: (o[k] if k.startswith(("image_", "depth_", "segmentation_")) or k in ("obs_stack", "point_cloud") else np.array(o[k], copy=True, order="C")) for k in self._keys}
 
     def _obs(self):
         return self._obs_from(self.sim.fetch_host())
@@ -124,6 +136,10 @@ class LowCostRobotVecEnv(_SB3VecEnv):
                 planes = sim.render_terminal_planes(env_ids)
             if sim.image_wrist is not None:   # (image_wrist and, with planes, depth_wrist / segmentation_wrist)
                 planes = {**planes, **sim.render_terminal_wrist(env_ids)}
+            if "obs_stack" in self._keys:      # (the stacks and the clouds of the episodes that ended, one batched call each as the frames are)
+                planes["obs_stack"] = sim.obs_stack_terminal(env_ids)
+            if "point_cloud" in self._keys:
+                planes["point_cloud"] = sim.point_cloud_terminal(env_ids)["point_cloud"]
         out = []
         for j, t in enumerate(tobs_rows):
             d = {"arm_qpos": t[0:6].copy(), "arm_qvel": t[6:12].copy()}
@@ -289,7 +305,15 @@ class LowCostRobotVectorEnv:
                     fin["image_wrist"] = np.zeros((self.num_envs,) + sim.image_size + (3,), np.uint8)
                 for k, a in sim.plane_arrays().items():
                     fin[k] = np.zeros((self.num_envs,) + sim.image_size, a.dtype)
+                if "obs_stack" in v._keys:
+                    fin["obs_stack"] = np.zeros(sim.obs_stack.shape, sim.obs_stack.dtype)
+                if "point_cloud" in v._keys:
+                    fin["point_cloud"] = np.zeros(sim.point_cloud.shape, np.float32)
                 if ridx.size:
+                    if "obs_stack" in v._keys:
+                        fin["obs_stack"][ridx] = sim.obs_stack_terminal(ridx)
+                    if "point_cloud" in v._keys:
+                        fin["point_cloud"][ridx] = sim.point_cloud_terminal(ridx)["point_cloud"]
                     fin["image_front"][ridx], fin["image_top"][ridx] = sim.render_terminal(ridx)
                     if sim.image_planes:
                         for k, a in sim.render_terminal_planes(ridx).items():

@@ -135,9 +135,12 @@ class VecSim:
             check(self.L.lcr_wrist_camera_check(ctypes.byref(wrist_camera)))
         # the observation stack (lcr_enable_obs_stack): None = none, an int = that many frames of every camera as uint8, or a dict of frames / cameras / dtype / reset_fill.
         # Checked here and by the library without a handle (lcr_obs_stack_check), before it is asked for a device
+        # terminal=True in the dict (lcr_enable_obs_stack_terminal): the library keeps the history of an episode that ends, obs_stack_terminal() returns its stack
+        stack_terminal = cloud_terminal = False
         if obs_stack is not None:
             if observation_mode == "state":
                 raise ValueError("obs_stack needs image observations: observation_mode 'image' or 'both'")
+            obs_stack, stack_terminal = _capi.take_terminal(obs_stack, "obs_stack")
             obs_stack = _capi.ObsStackSpec.from_any(obs_stack)
             if obs_stack.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
                 raise ValueError("obs_stack: cameras selects 'wrist', but no wrist_camera is given")
@@ -149,6 +152,8 @@ class VecSim:
         if point_cloud is not None:
             if observation_mode == "state":
                 raise ValueError("point_cloud needs image observations: observation_mode 'image' or 'both'")
+            # (`terminal`: the caller's declaration that they want the clouds of episodes that end -- point_cloud_terminal() needs no state and works without it)
+            point_cloud, cloud_terminal = _capi.take_terminal(point_cloud, "point_cloud")
             point_cloud, cloud_crop = _capi.PointCloudCrop.take(point_cloud)           # (`crop`: None without one)
             point_cloud, cloud_sampling = _capi.PointCloudSampling.take(point_cloud)   # (`sampling` and `pool`: the spec keeps its four fields)
             point_cloud = _capi.PointCloudSpec.from_any(point_cloud)
@@ -300,14 +305,22 @@ class VecSim:
                 self.depth_wrist = DeviceArray(self, wv.depth_wrist, pl, np.float32) if wv.depth_wrist else None
                 self.seg_wrist = DeviceArray(self, wv.seg_wrist, pl, np.uint8) if wv.seg_wrist else None
         self.obs_stack = self.obs_stack_spec = None
+        self.obs_stack_keeps_terminal = False   # obs_stack=dict(..., terminal=True): obs_stack_terminal() works
+        self.obs_stack_history = None           # ... and, with more than one frame, the history (N, K - 1, C, H, W) the library keeps for it
+        self.point_cloud_wants_terminal = cloud_terminal   # point_cloud=dict(..., terminal=True): what the vector adapters look at; point_cloud_terminal() works either way
         if obs_stack is not None:   # (last: behind look, wrist camera and planes)
             try:
-                check(self.L.lcr_enable_obs_stack(self.handle, ctypes.byref(obs_stack)))
+                check(self.L.lcr_enable_obs_stack_terminal(self.handle, ctypes.byref(obs_stack), int(stack_terminal)))   # (terminal False: lcr_enable_obs_stack)
                 sv = _capi.LcrObsStackView()
                 check(self.L.lcr_get_obs_stack(self.handle, ctypes.byref(sv)))
+                keep, hist, hist_bytes = ctypes.c_int32(0), ctypes.c_void_p(), ctypes.c_uint64(0)
+                check(self.L.lcr_get_obs_stack_terminal(self.handle, ctypes.byref(keep), ctypes.byref(hist), ctypes.byref(hist_bytes)))
             except Exception:
                 self.close()
                 raise
+            self.obs_stack_keeps_terminal = bool(keep.value)
+            if hist.value:
+                self.obs_stack_history = DeviceArray(self, hist.value, (N, int(sv.spec.frames) - 1, int(sv.channels)) + self.image_size, np.dtype(sv.spec.as_dict()["dtype"]))
             self.obs_stack_spec = sv.spec.as_dict()
             self.obs_stack = DeviceArray(self, sv.data, (N, int(sv.spec.frames), int(sv.channels)) + self.image_size, np.dtype(self.obs_stack_spec["dtype"]))
         self.point_cloud = self.point_cloud_count = self.point_cloud_source = self.point_cloud_pose = self.point_cloud_spec = None
@@ -460,6 +473,31 @@ class VecSim:
             out["depth_wrist"] = d
         if s is not None:
             out["segmentation_wrist"] = s
+        return out
+
+    def obs_stack_terminal(self, env_ids):
+        """the observation stacks of the episodes the last step ended in the listed envs (the sibling of render_terminal(), same precondition): (len(env_ids), K, C, H, W)
+        of the stack's element type -- the K - 1 frames the env's stack held before the step refilled it, then the terminal frames.  Needs obs_stack=dict(..., terminal=True)"""
+        if self.obs_stack is None:
+            raise ValueError("obs_stack_terminal: no obs_stack is enabled")
+        if not self.obs_stack_keeps_terminal:
+            raise ValueError("obs_stack_terminal: the obs_stack was enabled without terminal=True, so the history of an episode that ends is not kept")
+        ids = self._finished_ids("obs_stack_terminal", env_ids)
+        out = np.empty((ids.size,) + self.obs_stack.shape[1:], self.obs_stack.dtype)
+        check(self.L.lcr_obs_stack_terminal(self.handle, _vp(ids), int(ids.size), _vp(out)))
+        return out
+
+    def point_cloud_terminal(self, env_ids):
+        """the point clouds of the last observations of the episodes the last step ended in the listed envs (the sibling of render_terminal(), same precondition), made by
+        the sim's own cloud kernel from the terminal frames, planes, looks and poses: {"point_cloud": (len(env_ids), P, C) float32, "count": (len(env_ids),) int32,
+        "source": (len(env_ids), P) int32, "pose": (slots, 13, len(env_ids)) float32}.  Works on any sim with a point_cloud"""
+        if self.point_cloud is None:
+            raise ValueError("point_cloud_terminal: no point_cloud is enabled")
+        ids = self._finished_ids("point_cloud_terminal", env_ids)
+        n = ids.size
+        out = {"point_cloud": np.empty((n,) + self.point_cloud.shape[1:], np.float32), "count": np.empty(n, np.int32),
+               "source": np.empty((n,) + self.point_cloud_source.shape[1:], np.int32), "pose": np.empty(self.point_cloud_pose.shape[:2] + (n,), np.float32)}
+        check(self.L.lcr_point_cloud_terminal(self.handle, _vp(ids), int(n), _vp(out["point_cloud"]), _vp(out["count"]), _vp(out["source"]), _vp(out["pose"])))
         return out
 
     def look(self):

@@ -488,7 +488,8 @@ int lcr_render_terminal_wrist(lcr_sim *sim, const int32_t *env_ids_host, int cou
  *             and lcr_enable_look / lcr_enable_wrist_camera on a handle whose stack is on are refused.  The planes are not stacked; they may be enabled before or after.
  *   guards    the stack lies between two regions of LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, [data - LCR_WRIST_GUARD, data) and LCR_WRIST_GUARD bytes from the first
  *             256-byte boundary at or behind its end; filled once, never written afterwards.
- *   not kept  the stack of an episode that ended: the refill overwrites the K - 1 older frames of a reset env, so there is no stacked terminal observation. */
+ *   not kept  unless asked for, the stack of an episode that ended: the refill overwrites the K - 1 older frames of a reset env.  "Terminal observation stacks" below keeps
+ *             them (lcr_enable_obs_stack_terminal with keep_terminal = 1) and hands out the stacked terminal observation (lcr_obs_stack_terminal). */
 enum { LCR_STACK_CAM_FRONT = 1, LCR_STACK_CAM_TOP = 2, LCR_STACK_CAM_WRIST = 4 };
 typedef enum lcr_obs_stack_dtype { LCR_STACK_UINT8 = 0, LCR_STACK_FLOAT16 = 1, LCR_STACK_FLOAT32 = 2 } lcr_obs_stack_dtype;
 typedef enum lcr_obs_stack_fill { LCR_STACK_FILL_REPEAT = 0, LCR_STACK_FILL_ZERO = 1 } lcr_obs_stack_fill;
@@ -514,6 +515,34 @@ int lcr_obs_stack_check(const lcr_obs_stack_spec *spec);
 int lcr_enable_obs_stack(lcr_sim *sim, const lcr_obs_stack_spec *spec);
 /* The stack; waits (on the handle's stream) for frames and stack still being made on the second stream, as every entry point but the step does. */
 int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
+
+/* == Terminal observation stacks: the stack of an episode that has ended, for the consumers that owe SB3 / gymnasium a complete terminal_observation / final_obs, and for an
+ * on-device loop that bootstraps the value of a truncated episode.  The sibling of lcr_render_terminal for the stack.  Off unless asked for: a handle enabled with
+ * lcr_enable_obs_stack, or with keep_terminal = 0, launches the stack kernel it always launched and produces its bytes.
+ *   definition  env e was reset by the last lcr_step; before that step its slots 0 .. K - 1 held o(t-K+1) .. o(t).  Its terminal stack is [slots 1 .. K - 1 as they were before
+ *               that step's stack kernel ran, the terminal frame], newest last.  The terminal frame is what lcr_render_terminal (and lcr_render_terminal_wrist) draw for e,
+ *               of the stack's selected cameras, through the stack's element rule.  An episode shorter than K - 1 steps still shows its reset fill (repeat or zeros) in the
+ *               older slots -- what gymnasium's FrameStackObservation and SB3's VecFrameStack hold at that point.
+ *   history     with keep_terminal = 1 and K > 1 a device buffer [N][K - 1][C][H][W] of the element type, zero-filled when it is allocated.  The stack kernel of lcr_step, in
+ *               the build this mode launches, copies slots 1 .. K - 1 of every env whose did_reset is set to history[e] before it refills them (on the second stream it
+ *               reads the did_reset snapshot it already reads).  ONLY step refills save: the refills of lcr_reset, the rewrites of lcr_set_look and enabling leave the
+ *               history alone, and the history of an env stands until that env's next step reset.  K = 1 keeps nothing: the terminal stack is the terminal frame.
+ *   guards      the history lies behind the stack's second guard region, and LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE follow the first 256-byte boundary at or behind its
+ *               end; filled once, never written afterwards.
+ *   life        as the spec: the same spec and the same keep_terminal again do nothing, anything else is refused.
+ *   not kept    terminal history of the depth and segmentation planes; device-side outputs of the terminal calls. */
+/* lcr_enable_obs_stack with the choice to keep terminal stacks; lcr_enable_obs_stack(sim, spec) is this call with keep_terminal = 0.  `spec` is checked first, then
+ * keep_terminal (0 or 1: LCR_ERR_INVALID naming it), then the handle. */
+int lcr_enable_obs_stack_terminal(lcr_sim *sim, const lcr_obs_stack_spec *spec, int32_t keep_terminal);
+/* Whether terminal stacks are kept (*keep_terminal 1 / 0), the history (device, [N][K - 1][C][H][W]; NULL with K = 1 or without keep_terminal) and its bytes per env; joins
+ * as lcr_get_obs_stack does. */
+int lcr_get_obs_stack_terminal(lcr_sim *sim, int32_t *keep_terminal, const void **history, uint64_t *history_bytes_per_env);
+/* The terminal stacks of the listed envs, out_host [count][K][C][H][W] of the element type.  Synchronous; joins first.  Env ids are checked against the handle's range, and
+ * the precondition is that of lcr_render_terminal: every listed env was reset by the LAST lcr_step (the terminal poses, the terminal looks and the history belong to that
+ * step).  Refused (LCR_ERR_INVALID, naming which) on a handle without a stack and on one whose stack was enabled without keep_terminal.  count = 0 is LCR_OK.  The terminal
+ * frames are drawn and the stacks assembled in device staging, in as many passes as keep the staging -- per env the terminal frames of front, top and (if stacked) wrist and the
+ * terminal stack -- within the 450 MiB a pass of the terminal-frame calls takes. */
+int lcr_obs_stack_terminal(lcr_sim *sim, const int32_t *env_ids_host, int count, void *out_host);
 
 /* == The point cloud: an optional device buffer per handle, `points` [N][P][C] float32, that the library keeps current behind the frame kernels -- a fixed number of
  * world-frame points per env, fused over the cameras, floor and sky dropped: the input of a PointNet-style encoder or a 3-D diffusion policy.  Everything it is made of
@@ -547,7 +576,8 @@ int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
  *               after the observation stack.  Fixed for the life of the handle: the same spec again does nothing, another spec is refused.
  *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, points, the same guard from the first 256-byte boundary at or behind their end (as the
  *               stack has them), then count, source and camera_pose.  Freed by lcr_destroy.
- *   not in it   random sampling, normals, a base-frame transform, the cloud of an episode that has ended.  (Farthest-point sampling from a strided pool and a crop box
+ *   not in it   random sampling, normals, a base-frame transform.  Not KEPT either, and it need not be, is the cloud of an episode that has ended: lcr_point_cloud_terminal
+ *               ("The point cloud of the terminal observation" below) makes it from the terminal frames.  (Farthest-point sampling from a strided pool and a crop box
  *               are optional modes of their own: "The point cloud by farthest-point sampling" and "The point cloud inside a crop box" below.) */
 typedef struct lcr_point_cloud_spec {
     int32_t points;       /* P: a multiple of 64 in 64 .. 8192 */
@@ -649,6 +679,16 @@ int lcr_enable_point_cloud_cropped(lcr_sim *sim, const lcr_point_cloud_spec *spe
 /* The crop box of the handle's cloud: *enabled = 1 and the box in use, or *enabled = 0 and zeros for a cloud without a box and for a handle without a cloud; joins as
  * lcr_get_point_cloud does. */
 int lcr_get_point_cloud_crop(lcr_sim *sim, int32_t *enabled, lcr_point_cloud_crop *out);
+
+/* == The point cloud of the terminal observation: the sibling of lcr_render_terminal for the cloud.  It needs no state and no enabling step: per pass of the listed envs the
+ * library gathers their terminal poses and terminal looks, draws their terminal colour frames, both planes and -- if the cloud selects it -- the wrist camera's into device
+ * staging, and launches the handle's OWN cloud kernel (strided, farthest-point or cropped, with the handle's pool and box) over that view, with the wrist pose from the
+ * terminal joint angles.  The result is therefore, by construction, the function the three sections above define for the cloud, applied to the terminal frames, planes and
+ * cameras: what lcr_render_terminal, lcr_render_terminal_planes and lcr_render_terminal_wrist return for the same envs, and the cameras in `pose_host`.
+ *   outputs     points_host [count][P][C], count_host [count], source_host [count][P], pose_host [slots][13][count]; any of them may be NULL.
+ *   the rest    synchronous, joins first; env ids are checked against the handle's range; the precondition is that of lcr_render_terminal (every listed env was reset by the
+ *               LAST lcr_step).  A handle without a point cloud is refused (LCR_ERR_INVALID).  count = 0 is LCR_OK.  Nothing of the live cloud is touched. */
+int lcr_point_cloud_terminal(lcr_sim *sim, const int32_t *env_ids_host, int count, float *points_host, int32_t *count_host, int32_t *source_host, float *pose_host);
 
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
