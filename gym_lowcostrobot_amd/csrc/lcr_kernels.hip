@@ -991,7 +991,22 @@ DEV bool substep(const LcrDev &P, EnvState<NC> &S, const float (&ctrl)[6], float
         const int row0[NAS] = {arm_row0_of<ROLL, NC, BIG, NEWTON>(0), arm_row0_of<ROLL, NC, BIG, NEWTON>(1), arm_row0_of<ROLL, NC, BIG, NEWTON>(2),
                                arm_row0_of<ROLL, NC, BIG, NEWTON>(3), arm_row0_of<ROLL, NC, BIG, NEWTON>(4)};
         const NewtonParams NP = newton_params(P);
-        NewtonCtx<NC, NRW, WALLS, NCC> C{NP, lds, lane, row0, AS, slot_any, link_on_cube, slot_cube, FS, WS, wsg, wall_any,
+        // Which arm slots the SIMT solves visit.  Invariant of the fast copy: a coupled lane is never enabled for the arm (C.enable below has its arm bit clear), and a
+        // real lane with AS[0].act, AS[1].act or AS[4].act on a cube IS coupled (set-up above; `coupled` is final here).  The fast copy's only solve over the arm is
+        // the small one, so an arm slot that only coupled lanes have active adds exact zeros for every lane that solve moves, and its forces in the coupled lanes are
+        // written by the cooperative solve afterwards: the slot is not visited.  In a wave of real lanes that takes out the finger-on-cube slots 0 and 1 -- the
+        // dearest: six rows, three of them rebuilt from three body rows in LDS each -- for good, and a floor or proxy slot that only a patient has.  (The shadow lanes
+        // of a ragged last wave copy the last env, are nobody's patient and keep such a slot switched on for their wave; they store nothing.)  The mask goes in as the
+        // context's slot_any; the set-up above and the cooperative solves (staged records: act per block) do not read it.  The same mask for the joint-limit rows and
+        // the slots 0 and 1 as compile-time literals were measured and left out: DESIGN section 0d
+        bool slot_solve[NAS];
+#pragma unroll
+        for (int s = 0; s < NAS; s++) slot_solve[s] = slot_any[s];
+        if constexpr (CPL == CPL_FAST) {
+#pragma unroll
+            for (int s = 0; s < NAS; s++) slot_solve[s] = slot_any[s] && __any(AS[s].act && !coupled) != 0;
+        }
+        NewtonCtx<NC, NRW, WALLS, NCC> C{NP, lds, lane, row0, AS, slot_solve, link_on_cube, slot_cube, FS, WS, wsg, wall_any,
                                          ccl, cc_act, cc_any, ccn, cct1, cct2, S.cp, lim_act, lim_wave, S.q, S.qd, CL, flim, y0s};
         const long long tn0 = P.diag == 2 ? clock64() : 0;   // (profiling aid: cycles of the solves, of the coupled ones, iterations -- tools/newton_phases.py)
         bool prof_coupled = false;

@@ -283,7 +283,10 @@ DEV int newton_solve(NewtonCtx<NC, NRW, WALLS, NCC> &C, float (&y)[6], f3 (&ca)[
         m2[3] = s < 2 ? P.mu_fct2 : (s < 4 ? MU_TORS * MU_TORS : (oncube ? P.mu_ct2 : 0.f));
         m2[4] = m2[5] = s < 2 ? P.mu_fcr2 : (s < 4 ? MU_ROLL * MU_ROLL : 0.f);
     };
-    // which arm slots exist in this problem, and whether their rows carry a cube share here
+    // which arm slots exist in this problem, and whether their rows carry a cube share here.  slot_any is wave-uniform and the CALLER's statement of
+    // what this solve has to visit: a slot that is on costs all 64 lanes its rows in dots, assemble, every ls_eval and kink_cand, a lane without the contact adding
+    // exact zeros (blk_eval of an inactive block: f = 0, av = gam = kap = 0).  The coupled copies pass "some lane has it active"; the fast copy passes "some lane that
+    // is not coupled has it active" -- its coupled lanes sit the arm solve out (C.enable) and get every force from the cooperative solve (lcr_kernels.hip)
     auto arm_here = [&](int s) -> bool { return HAS_A && C.slot_any[s]; };
     auto arm_cube_part = [&](int s) -> bool { return ARM_CUBE && (s < 2 || (s == 4 && wave_cube4)); };
     // the dense row r of arm slot s in the compact coordinates: g row from LDS, the cube's share in closed form
