@@ -52,7 +52,7 @@ SYMBOLS = [
     "lcr_create", "lcr_destroy", "lcr_set_stream", "lcr_sync", "lcr_reset", "lcr_step", "lcr_step_host",
     "lcr_get_obs", "lcr_get_outputs", "lcr_fetch_host", "lcr_get_state", "lcr_set_state", "lcr_malloc", "lcr_free",
     "lcr_memcpy_h2d", "lcr_memcpy_d2h", "lcr_timer_begin", "lcr_timer_end", "lcr_fill_random_actions",
-    "lcr_calibrate_copy", "lcr_render", "lcr_render_state", "lcr_render_terminal", "lcr_step_kernel_family",
+    "lcr_calibrate_copy", "lcr_render", "lcr_render_state", "lcr_render_terminal", "lcr_step_kernel_family", "lcr_get_redo_flags",
     "lcr_enable_image_planes", "lcr_get_image_planes", "lcr_render_planes", "lcr_render_state_planes", "lcr_render_terminal_planes",
     "lcr_look_variant_default", "lcr_enable_look", "lcr_set_look", "lcr_get_look",
     "lcr_wrist_camera_default", "lcr_wrist_camera_check", "lcr_enable_wrist_camera", "lcr_get_wrist_camera", "lcr_render_terminal_wrist",
@@ -578,6 +578,7 @@ def load():
     L.lcr_destroy.argtypes = [vp]
     L.lcr_destroy.restype = None
     L.lcr_step_kernel_family.argtypes = [vp]
+    L.lcr_get_redo_flags.argtypes = [vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.lcr_set_stream.argtypes = [vp, vp]
     L.lcr_sync.argtypes = [vp]
     L.lcr_reset.argtypes = [vp, vp, vp]

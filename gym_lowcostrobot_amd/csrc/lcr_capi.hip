@@ -127,6 +127,8 @@ struct lcr_sim {
     hipStream_t stream;
     void *arena;        // one allocation holding every SoA array
     size_t arena_bytes;
+    LcrRedo redo;            // one-cube Newton kernels: the per-wave flags of the pair of launches and whether the pair runs (lcr_device.h)
+    size_t redo_words;       // ints of redo.flags (0: this handle's step kernel keeps no such flags)
     float *action_stage;     // [k][N] staging for lcr_step_host
     unsigned char *mask_dev; // [N]
     unsigned long long *seeds_dev; // [N]
@@ -535,6 +537,11 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     const size_t o_img0 = C.take(s->has_images ? img_bytes * N : 0);
     const size_t o_img1 = C.take(s->has_images ? img_bytes * N : 0);
     const size_t o_bg = C.take(s->has_images ? 2 * img_bytes : 0);
+    // one-cube Newton kernel: a flag per wave, for the launch that repeats the control step of waves the fast-copy-only kernel gave up on (lcr_kernels.hip: STEP_FAST_ONLY).
+    // The workgroup's four waves read their four words: rounded up; the words of waves past the last env stay zero
+    const bool redo_wg = cfg->solver == LCR_SOLVER_NEWTON && cfg->task != LCR_TASK_STACK && cfg->task != LCR_TASK_PUSH_LOOP;
+    const size_t redo_words = redo_wg ? ((N + 255) / 256) * 4 : 0;
+    const size_t o_redo = C.take(sizeof(int) * redo_words);
     const size_t off = C.off;
     s->arena_bytes = off;
     s->fetch_bytes = o_fetch_end;
@@ -675,6 +682,10 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     D.ctrl_out = cfg->diagnostics ? (float *)(base + o_dctrl) : nullptr;
     D.scratch = (float *)(base + o_scr);
     D.warm = carry_warm ? (float *)(base + o_warm) : nullptr;
+    s->redo.flags = redo_words ? (int *)(base + o_redo) : nullptr;
+    s->redo.gate = redo_words ? 1 : 0;
+    if (const char *ov = getenv("LCR_REDO_KERNEL")) { if (atoi(ov) == 0) s->redo.gate = 0; }   // (A/B runs and tests: the kernel with both substep copies alone, as before the pair)
+    s->redo_words = redo_words;
     D.img_front = s->has_images ? (unsigned char *)(base + o_img0) : nullptr;
     D.img_top = s->has_images ? (unsigned char *)(base + o_img1) : nullptr;
     D.img_bg = s->has_images ? (unsigned char *)(base + o_bg) : nullptr;
@@ -759,6 +770,18 @@ int lcr_step_kernel_family(lcr_sim *s) {
     return s->dev.coop;
 }
 
+int lcr_get_redo_flags(lcr_sim *s, int32_t *flags_host, int32_t capacity, int32_t *n_waves, int32_t *paired) {
+    SIMCHK(s);
+    const int waves = (s->dev.n + 63) / 64;
+    if (n_waves) *n_waves = s->redo_words ? waves : 0;
+    if (paired) *paired = s->redo.gate;
+    if (!flags_host || !s->redo_words) return LCR_OK;
+    if (capacity < waves) return fail(LCR_ERR_INVALID, "flags_host holds %d words, the handle has %d waves", capacity, waves);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(flags_host, s->redo.flags, sizeof(int32_t) * (size_t)waves, hipMemcpyDeviceToHost));
+    return LCR_OK;
+}
+
 int lcr_set_stream(lcr_sim *s, void *hip_stream) {
     SIMCHK(s);
     // nothing enqueued on the old stream -- a step kernel, a reset, lcr_fill_random_actions into a buffer the next step reads -- is in flight when the new stream takes over:
@@ -793,7 +816,7 @@ int lcr_reset(lcr_sim *s, const uint8_t *mask_host, const uint64_t *seeds_host) 
 int lcr_step(lcr_sim *s, const float *action_dev) {
     SIMCHK_NOJOIN(s);
     if (!action_dev) return fail(LCR_ERR_INVALID, "action is NULL");
-    LAUNCHCHK("step kernel", lcr_launch_step(s->dev, action_dev, s->ee_mode, s->stream));
+    LAUNCHCHK("step kernel", lcr_launch_step(s->dev, action_dev, s->ee_mode, s->stream, s->redo));
     if (s->look_K)   // envs the step has auto-reset: their look becomes the terminal look, they count an episode and draw its look -- before the snapshot below
         LAUNCHCHK("look kernel", lcr_launch_look_redraw(s->dev.n, s->dev.env_off, s->dev.did_reset, 0, s->look_sm, s->look_cur, s->look_episode, s->look_term, s->stream));
     if (s->has_images && s->rstream) {

@@ -78,6 +78,13 @@ struct LcrDev {
     int img_epw;                     // frame kernel: envs per workgroup (1, 2 or 4), chosen from the frame size at lcr_create (lcr_render.hip)
 };
 
+// The one-cube Newton kernel as a pair of launches (lcr_kernels.hip: STEP_FAST_ONLY): the kernel with the fast substep copy alone, then the kernel with both copies for
+// the waves the first one flagged.  A kernel argument of its own, as LcrPlanes is: LcrDev, and with it the code of every other kernel, stays as it is
+struct LcrRedo {
+    int *flags;   // [ceil(n / 64) rounded up to the workgroup's four waves] 1: the wave bailed out of the last step's first launch; null: a kernel without the pair
+    int gate;     // 1: the pair (default); 0: the kernel with both copies alone, ungated (LCR_REDO_KERNEL=0)
+};
+
 // pinhole camera: position, world axes (camera looks along -Z), s = 2 tan(fovy/2) / height
 struct LcrCam {
     float px, py, pz;
@@ -132,9 +139,9 @@ struct LcrWrist {
 };
 
 // launchers implemented in lcr_kernels.hip / lcr_render.hip (plain C++ linkage, same shared object)
-int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
+int lcr_launch_step(const LcrDev &P, const float *action_dev, int ee_mode, void *stream, const LcrRedo &redo);
 // the Newton kernels of the faithful preset (lcr_kernels.hip, unit LCR_PART = 4)
-int lcr_launch_step_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);
+int lcr_launch_step_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream, const LcrRedo &redo);   // (the pair of launches, or the second kernel alone: LcrRedo)
 int lcr_launch_step_newton_stack(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);   // (unit LCR_PART = 5)
 int lcr_launch_step_loop_newton(const LcrDev &P, const float *action_dev, int ee_mode, void *stream);    // (PushCubeLoop: one wave per 64 envs, unit LCR_PART = 7)
 // two-cooperating-waves family (lcr_kernels2.hip); occ = waves per SIMD the variant is compiled for

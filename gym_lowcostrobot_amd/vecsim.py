@@ -661,6 +661,18 @@ class VecSim:
             "did_reset": self.did_reset.numpy().astype(bool),
         }
 
+    def redo_flags(self):
+        """Debug accessor: per 64-env wave, whether the LAST step repeated its control step in the second launch of the one-cube Newton kernels' pair
+        (lcr_get_redo_flags); None for a handle whose step kernel keeps no such flags.  `redo_paired` says whether the pair runs (LCR_REDO_KERNEL=0: not)."""
+        n_waves, paired = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(self.L.lcr_get_redo_flags(self.handle, None, 0, ctypes.byref(n_waves), ctypes.byref(paired)))
+        self.redo_paired = bool(paired.value)
+        if n_waves.value == 0:
+            return None
+        flags = np.zeros(n_waves.value, np.int32)
+        check(self.L.lcr_get_redo_flags(self.handle, _vp(flags), n_waves.value, None, None))
+        return flags.astype(bool)
+
     def get_state(self):
         N = self.n
         st = {

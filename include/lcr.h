@@ -218,6 +218,7 @@ typedef struct lcr_host_view {
 /* Environment variables the library reads (measurement / A-B overrides, none needed in production; all read at lcr_create unless stated):
  *   LCR_COOP_MAX=n        Newton kernels: coupled envs per wave solved cooperatively before the wave falls back to the coupled SIMT solves (default 8; 16 for
  *                         StackTwoCubes and PushCubeLoop; 0 = never cooperatively)
+ *   LCR_REDO_KERNEL=0     one-cube Newton kernel: the kernel with both substep copies alone instead of the fast-copy-only kernel followed by it (lcr_get_redo_flags)
  *   LCR_RENDER_OVERLAP=0  image observations: frames on the handle's stream after the step kernel instead of on the second stream (see lcr_step)
  *   LCR_STEP_KERNEL=single|coop1|coop2, LCR_STACK_LDS=small|big   sweep kernels (LCR_PRESET_FAST): pin a kernel family / LDS variant
  *   LCR_RENDER_EPW=1|2|4  frame kernel, frames up to 170 px wide: envs per workgroup instead of the choice by frame size (tools/frame_sizes.py; same bytes under all three)
@@ -242,6 +243,14 @@ void lcr_destroy(lcr_sim *sim); /* == close() reach_cube_env.py:357-363; frees e
 /* Which step-kernel family this handle runs (decided at lcr_create from lcr_config.step_kernel and the shard size): 0 = one wave per 64 envs
  * (lcr_step_kernel), 1 / 2 = two cooperating waves per 64 envs (lcr_step2_kernel) compiled for one / two waves per SIMD. */
 int lcr_step_kernel_family(lcr_sim *sim);
+
+/* Debug accessor (tests, profiling).  The one-cube tasks under LCR_SOLVER_NEWTON step with a pair of launches: a kernel that holds only the substep copy with
+ * 6-dimensional solves, and behind it the kernel with the coupled SIMT copy as well, which repeats -- from the untouched state -- the control step of the 64-env waves
+ * that gave up in the first (more than LCR_COOP_MAX coupled envs in a substep) and leaves at once when there is none.  flags_host[w] (capacity >= ceil(N / 64) words;
+ * NULL: only the counts) is 1 if wave w went through the second launch in the LAST lcr_step; a host wait on the handle's stream.  *n_waves: ceil(N / 64), or 0 for
+ * a handle whose kernel keeps no such flags (every other task / solver; the flags are then not written).  *paired: 1 the pair, 0 the second kernel alone and ungated
+ * (LCR_REDO_KERNEL=0: the flags stay zero). */
+int lcr_get_redo_flags(lcr_sim *sim, int32_t *flags_host, int32_t capacity, int32_t *n_waves, int32_t *paired);
 
 /* HIP stream (hipStream_t passed as void*) all later work is enqueued on; NULL = default stream.  Synchronises the OLD stream (a host wait, after making it wait for
  * frames still being ray-cast) before it switches: whatever was enqueued on it -- a step, a reset, lcr_fill_random_actions -- has finished when work on the new stream
