@@ -42,6 +42,9 @@ CLOUD_DEFAULT_IDS = 0x7FC   # LCR_CLOUD_DEFAULT_IDS: arm, cube, cube2
 CLOUD_MIN_POINTS, CLOUD_MAX_POINTS = 64, 8192
 CLOUD_SAMPLINGS = {"stride": 0, "fps": 1}   # LCR_CLOUD_SAMPLE_*: the strided selection, or farthest-point sampling from a strided pool (lcr_enable_point_cloud_sampled)
 CLOUD_MAX_POOL = 4096                       # LCR_CLOUD_MAX_POOL
+# the voxel grid (lcr_enable_voxel_grid): LCR_VOXEL_* feature bits, LCR_VOXEL_MAX_DIM, LCR_VOXEL_MAX_CELLS; its cameras, ids and dtypes are the cloud's and the stack's
+VOXEL_FEATURES = {"occupancy": 1, "rgb": 2}
+VOXEL_MAX_DIM, VOXEL_MAX_CELLS = 64, 32768
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -61,6 +64,7 @@ SYMBOLS = [
     "lcr_point_cloud_sampling_check", "lcr_enable_point_cloud_sampled", "lcr_get_point_cloud_sampling",
     "lcr_point_cloud_crop_check", "lcr_enable_point_cloud_cropped", "lcr_get_point_cloud_crop",
     "lcr_enable_obs_stack_terminal", "lcr_get_obs_stack_terminal", "lcr_obs_stack_terminal", "lcr_point_cloud_terminal",
+    "lcr_voxel_grid_check", "lcr_enable_voxel_grid", "lcr_get_voxel_grid",
 ]
 
 
@@ -492,6 +496,130 @@ class LcrPointCloudView(ctypes.Structure):
     ]
 
 
+class VoxelGridSpec(ctypes.Structure):
+    """lcr_voxel_grid_spec: box, cells, cameras, surface ids, channels and element type of the voxel grid (include/lcr.h)"""
+    _fields_ = [
+        ("lo", ctypes.c_float * 3),      # x, y, z of the box's lower corner, world frame; finite
+        ("hi", ctypes.c_float * 3),      # x, y, z of the upper corner; finite, lo[k] < hi[k]
+        ("dims", ctypes.c_int32 * 3),    # Dx (a multiple of 4), Dy, Dz: each 1 .. VOXEL_MAX_DIM, at most VOXEL_MAX_CELLS voxels
+        ("cameras", ctypes.c_uint32),    # STACK_CAMERAS bits; 0 = every camera the handle has
+        ("ids", ctypes.c_uint32),        # bit i: surface id i is a candidate (1 .. 10); 0 = CLOUD_DEFAULT_IDS
+        ("features", ctypes.c_uint32),   # VOXEL_FEATURES bits; occupancy is implied
+        ("dtype", ctypes.c_int32),       # STACK_DTYPES: uint8 or float32
+        ("source", ctypes.c_int32),      # 0 | 1: keep the source index of every voxel
+    ]
+
+    def as_dict(self):
+        """the float32 corners in use as Python floats, cameras / features as names, ids as a tuple, as PointCloudSpec.as_dict has them"""
+        return {"lo": tuple(float(v) for v in self.lo), "hi": tuple(float(v) for v in self.hi), "dims": tuple(int(v) for v in self.dims),
+                "cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b), "ids": tuple(i for i in range(32) if self.ids >> i & 1),
+                "features": tuple(n for n, b in VOXEL_FEATURES.items() if self.features & b),
+                "dtype": {v: k for k, v in STACK_DTYPES.items()}.get(int(self.dtype), int(self.dtype)), "source": bool(self.source)}
+
+    @classmethod
+    def from_any(cls, v):
+        """a VoxelGridSpec, or a dict with box=((x0, y0, z0), (x1, y1, z1)) and dims=(Dx, Dy, Dz) -- neither has a default: the caller chooses the memory -- and some of
+        cameras / ids / features / dtype / source"""
+        import numpy as np
+
+        if isinstance(v, cls):
+            return v
+        if not isinstance(v, dict):
+            raise ValueError(f"voxel_grid must be None or a dict of box / dims / cameras / ids / features / dtype / source, got {v!r}")
+        v = dict(v)
+        out = cls()
+        if "box" not in v or "dims" not in v:
+            raise ValueError("voxel_grid needs box=((x0, y0, z0), (x1, y1, z1)) and dims=(Dx, Dy, Dz): neither has a default, the caller chooses the memory")
+        box, dims = v.pop("box"), v.pop("dims")
+        what = "voxel_grid: box must be ((x0, y0, z0), (x1, y1, z1)), the lower and the upper corner of a box in the world frame, six finite numbers"
+        try:
+            lo, hi = box
+            lo, hi = list(lo), list(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}, got {box!r}") from None
+        if isinstance(box, str) or len(lo) != 3 or len(hi) != 3:
+            raise ValueError(f"{what}, got {box!r}")
+        for name, side, dst in (("lo", lo, out.lo), ("hi", hi, out.hi)):
+            for k, x in enumerate(side):
+                if isinstance(x, (bool, np.bool_, str)) or not isinstance(x, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"{what}; {name}[{k}] is {x!r}")
+                x = np.float32(x)   # (the float32 value the kernel subtracts)
+                if not np.isfinite(x):
+                    raise ValueError(f"voxel_grid: box {name}[{k}] is not finite: the box of a voxel grid has no open sides")
+                dst[k] = float(x)
+        for k, axis in enumerate("xyz"):
+            if not out.lo[k] < out.hi[k]:
+                raise ValueError(f"voxel_grid: box lo[{k}] >= hi[{k}]: the box is empty along {axis} (lo {out.lo[k]!r}, hi {out.hi[k]!r})")
+        try:
+            dims = list(dims)
+        except TypeError:
+            dims = []
+        if len(dims) != 3 or any(isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, np.integer)) or not 1 <= d <= VOXEL_MAX_DIM for d in dims):
+            raise ValueError(f"voxel_grid: dims must be (Dx, Dy, Dz), each an integer in 1 .. {VOXEL_MAX_DIM}, got {dims!r}")
+        if dims[0] % 4:
+            raise ValueError(f"voxel_grid: dims[0] (x) must be a multiple of 4, got {dims[0]!r}")
+        if dims[0] * dims[1] * dims[2] > VOXEL_MAX_CELLS:
+            raise ValueError(f"voxel_grid: dims {tuple(dims)!r} are {dims[0] * dims[1] * dims[2]} voxels: at most {VOXEL_MAX_CELLS}")
+        for k in range(3):
+            out.dims[k] = int(dims[k])
+        cams = v.pop("cameras", None)
+        if cams is not None:
+            if isinstance(cams, str) or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"voxel_grid: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        ids = v.pop("ids", None)
+        if ids is not None:
+            mask = 0
+            ok = not isinstance(ids, str) and hasattr(ids, "__iter__")
+            for i in (ids if ok else ()):
+                if isinstance(i, str) and i in CLOUD_IDS:
+                    mask |= CLOUD_IDS[i]
+                elif isinstance(i, (int, np.integer)) and not isinstance(i, (bool, np.bool_)) and 1 <= i <= 10:
+                    mask |= 1 << int(i)
+                else:
+                    ok = False
+            if not ok or mask == 0:
+                raise ValueError(f"voxel_grid: ids must be a non-empty tuple drawn from 'arm', 'cube', 'cube2', 'floor' and the surface ids 1 .. 10, got {ids!r}")
+            out.ids = mask
+        feats = v.pop("features", ("occupancy",))
+        if isinstance(feats, str) or not hasattr(feats, "__iter__") or not all(isinstance(f, str) and f in VOXEL_FEATURES for f in feats):
+            raise ValueError(f"voxel_grid: features must be a tuple drawn from 'occupancy' (implied) and 'rgb', got {feats!r}")
+        out.features = VOXEL_FEATURES["occupancy"] | sum(VOXEL_FEATURES[f] for f in set(feats))
+        dtype = v.pop("dtype", "uint8")
+        try:
+            dtype = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+        except TypeError:
+            pass
+        if dtype not in ("uint8", "float32"):
+            raise ValueError(f"voxel_grid: dtype must be 'uint8' or 'float32', got {dtype!r}")
+        out.dtype = STACK_DTYPES[dtype]
+        source = v.pop("source", False)
+        if not isinstance(source, (bool, np.bool_)):
+            raise ValueError(f"voxel_grid: source must be a bool, got {source!r}")
+        out.source = int(source)
+        if v:
+            raise ValueError(f"unknown voxel_grid fields {sorted(v)}")
+        return out
+
+
+class LcrVoxelGridView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", VoxelGridSpec),           # cameras and ids resolved to the bits in use, the occupancy bit set
+        ("inv_cell", ctypes.c_float * 3),  # cells per metre along x, y, z: the float32 values the kernel multiplies with
+        ("channels", ctypes.c_int32),
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("voxels", ctypes.c_void_p),       # [N][C][Dz][Dy][Dx] of the element type
+        ("source", ctypes.c_void_p),       # [N][Dz][Dy][Dx] int32, or NULL
+        ("count", ctypes.c_void_p),        # [N] int32
+        ("occupied", ctypes.c_void_p),     # [N] int32
+        ("camera_pose", ctypes.c_void_p),  # [slots][13][N] float32
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -630,6 +758,9 @@ def load():
     L.lcr_get_obs_stack_terminal.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(u64)]
     L.lcr_obs_stack_terminal.argtypes = [vp, vp, ctypes.c_int, vp]
     L.lcr_point_cloud_terminal.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
+    L.lcr_voxel_grid_check.argtypes = [ctypes.POINTER(VoxelGridSpec)]
+    L.lcr_enable_voxel_grid.argtypes = [vp, ctypes.POINTER(VoxelGridSpec)]
+    L.lcr_get_voxel_grid.argtypes = [vp, ctypes.POINTER(LcrVoxelGridView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

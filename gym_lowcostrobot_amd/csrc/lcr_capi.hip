@@ -15,6 +15,7 @@
 #include "lcr_model_gen.h"
 #include "lcr_stack.h"
 #include "lcr_cloud.h"
+#include "lcr_voxel.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -191,6 +192,12 @@ struct lcr_sim {
     bool cloud_crop_on;                // a crop box (lcr_enable_point_cloud_cropped): the kernels of lcr_cloud_crop.hip make the cloud
     lcr_point_cloud_crop cloud_crop;
     void *cloud_mem;
+    // the voxel grid (lcr_enable_voxel_grid): one allocation -- guard, voxels, guard, source, count, occupied, camera poses --, fixed for the life of the handle
+    bool voxel_on;
+    lcr_voxel_grid_spec voxel_spec;    // as enabled, cameras, ids and features resolved
+    LcrVoxel voxel;                    // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
+    void *voxel_mem;
+    size_t voxel_bytes_per_env;
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -245,12 +252,23 @@ static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     return lcr_launch_point_cloud(A, stream);
 }
 
+// the grid kernel, behind the frame kernels (the stack kernel and the cloud kernel) on their stream: the grid of P's envs from the frames just drawn, with the cameras that
+// drew them and the wrist pose from P's qpos, as launch_cloud passes them
+static int launch_voxel(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
+    LcrVoxel A = s->voxel;
+    A.front = s->cam_front; A.top = s->cam_top;
+    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
+    A.qpos = P.qpos;
+    return lcr_launch_voxel_grid(A, stream);
+}
+
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
-// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), and on a handle with a point cloud its kernel last
+// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, and on one with a voxel grid its kernel last
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
     if (s->cloud_on) LAUNCHCHK("point-cloud kernel", launch_cloud(s, P, stream, look));
+    if (s->voxel_on) LAUNCHCHK("voxel-grid kernel", launch_voxel(s, P, stream, look));
     return LCR_OK;
 }
 
@@ -752,6 +770,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->wrist_mem) (void)hipFree(s->wrist_mem);
     if (s->stack_mem) (void)hipFree(s->stack_mem);
     if (s->cloud_mem) (void)hipFree(s->cloud_mem);
+    if (s->voxel_mem) (void)hipFree(s->voxel_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -1969,6 +1988,145 @@ int lcr_point_cloud_terminal(lcr_sim *s, const int32_t *env_ids_host, int count,
             HIPCHK(hipMemcpy2DAsync(pose_host + done, sizeof(float) * count, buf[12], sizeof(float) * c, sizeof(float) * c, (size_t)s->cloud.slots * 13, hipMemcpyDeviceToHost, s->stream));
         return LCR_OK;
     });
+}
+
+// ---- the voxel grid ----
+
+static const char *voxel_dtype_name(int dtype) { return dtype == LCR_STACK_FLOAT32 ? "float32" : "uint8"; }
+
+int lcr_voxel_grid_check(const lcr_voxel_grid_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    static const char *const axis = "xyz";
+    // (by the bits, read as an integer from the struct: this unit is built with -ffast-math, under which no test of a float VALUE for NaN or infinity survives)
+    const auto finite = [](const float *v) { uint32_t b; memcpy(&b, v, sizeof b); return (b & 0x7f800000u) != 0x7f800000u; };
+    for (int k = 0; k < 3; k++) {
+        if (!finite(&spec->lo[k])) return fail(LCR_ERR_INVALID, "lo[%d] (%c) is not finite: the box of a voxel grid has no open sides", k, axis[k]);
+        if (!finite(&spec->hi[k])) return fail(LCR_ERR_INVALID, "hi[%d] (%c) is not finite: the box of a voxel grid has no open sides", k, axis[k]);
+    }
+    for (int k = 0; k < 3; k++)
+        if (!(spec->lo[k] < spec->hi[k]))
+            return fail(LCR_ERR_INVALID, "lo[%d] >= hi[%d]: the box is empty along %c (lo %.9g, hi %.9g)", k, k, axis[k], (double)spec->lo[k], (double)spec->hi[k]);
+    for (int k = 0; k < 3; k++)
+        if (spec->dims[k] < 1 || spec->dims[k] > LCR_VOXEL_MAX_DIM)
+            return fail(LCR_ERR_INVALID, "dims[%d] (%c) must be in 1 .. %d, got %d", k, axis[k], LCR_VOXEL_MAX_DIM, spec->dims[k]);
+    if (spec->dims[0] % 4 != 0) return fail(LCR_ERR_INVALID, "dims[0] (x) must be a multiple of 4 (the kernel writes four voxels along x at a time), got %d", spec->dims[0]);
+    if ((int64_t)spec->dims[0] * spec->dims[1] * spec->dims[2] > LCR_VOXEL_MAX_CELLS)
+        return fail(LCR_ERR_INVALID, "dims %d x %d x %d are %lld voxels: at most %d", spec->dims[0], spec->dims[1], spec->dims[2],
+                    (long long)spec->dims[0] * spec->dims[1] * spec->dims[2], LCR_VOXEL_MAX_CELLS);
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be a mask of 1 (front), 2 (top) and 4 (wrist), or 0 for every camera of the handle, got %u", spec->cameras);
+    if (spec->ids & ~(uint32_t)0x7FEu)
+        return fail(LCR_ERR_INVALID, "ids must be a mask over the surface ids 1 .. 10 (bits 1 .. 10; bit 0 is the sky, which is no surface), or 0 for arm and cubes (0x7FC), got 0x%x", spec->ids);
+    if (spec->features & ~(uint32_t)(LCR_VOXEL_OCCUPANCY | LCR_VOXEL_RGB))
+        return fail(LCR_ERR_INVALID, "features must be a mask of 1 (occupancy, implied) and 2 (rgb), got %u", spec->features);
+    if (spec->dtype != LCR_STACK_UINT8 && spec->dtype != LCR_STACK_FLOAT32)
+        return fail(LCR_ERR_INVALID, "dtype must be 0 (uint8) or 2 (float32): a voxel grid has no float16 elements, got %d", spec->dtype);
+    if (spec->source != 0 && spec->source != 1) return fail(LCR_ERR_INVALID, "source must be 0 or 1, got %d", spec->source);
+    return LCR_OK;
+}
+
+// "box (x y z) .. (x y z), dims a x b x c, cameras, ids, features, dtype, source" into buf: how the refusal names a spec
+static const char *voxel_spec_text(char (&buf)[320], const lcr_voxel_grid_spec &v) {
+    snprintf(buf, sizeof buf, "box (%.9g %.9g %.9g) .. (%.9g %.9g %.9g), dims %d x %d x %d, cameras %u, ids 0x%x, features %u, dtype %s, source %d", (double)v.lo[0], (double)v.lo[1],
+             (double)v.lo[2], (double)v.hi[0], (double)v.hi[1], (double)v.hi[2], v.dims[0], v.dims[1], v.dims[2], v.cameras, v.ids, v.features, voxel_dtype_name(v.dtype), v.source);
+    return buf;
+}
+
+int lcr_enable_voxel_grid(lcr_sim *s, const lcr_voxel_grid_spec *spec) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_voxel_grid_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a voxel grid of");
+    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
+    if ((s->planes & both) != both)
+        return fail(LCR_ERR_INVALID, "the voxel grid needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the grid): %s",
+                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
+    lcr_voxel_grid_spec sp = *spec;
+    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
+    sp.features |= LCR_VOXEL_OCCUPANCY;
+    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the grid)");
+    if (s->voxel_on) {
+        // (the boxes compare as float32 values: the kernel then forms the same cells; no corner is a NaN)
+        bool same = memcmp(sp.dims, s->voxel_spec.dims, sizeof sp.dims) == 0 && sp.cameras == s->voxel_spec.cameras && sp.ids == s->voxel_spec.ids &&
+                    sp.features == s->voxel_spec.features && sp.dtype == s->voxel_spec.dtype && sp.source == s->voxel_spec.source;
+        for (int k = 0; k < 3 && same; k++) same = sp.lo[k] == s->voxel_spec.lo[k] && sp.hi[k] == s->voxel_spec.hi[k];
+        if (same) return LCR_OK;
+        char was[320], asked[320];
+        return fail(LCR_ERR_INVALID, "a voxel grid (%s) is enabled already and fixed for the life of the handle: asked for %s", voxel_spec_text(was, s->voxel_spec), voxel_spec_text(asked, sp));
+    }
+    LcrVoxel A{};
+    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
+        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
+    };
+    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
+    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
+    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    const size_t N = (size_t)s->dev.n, V = (size_t)sp.dims[0] * sp.dims[1] * sp.dims[2], Cn = (sp.features & LCR_VOXEL_RGB) ? 4 : 1, esize = sp.dtype == LCR_STACK_FLOAT32 ? 4 : 1;
+    // guard, voxels, guard (include/lcr.h: LCR_WRIST_GUARD), then source, count, occupied and the camera poses
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_vox = C.take(N * Cn * V * esize);
+    C.skip(LCR_WRIST_GUARD);
+    const size_t guarded = C.off;
+    const size_t o_src = C.take(sp.source ? N * V * sizeof(int) : 0);
+    const size_t o_cnt = C.take(N * sizeof(int));
+    const size_t o_occ = C.take(N * sizeof(int));
+    const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
+    const size_t off = C.off;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the voxel grid failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.ids = sp.ids;
+    for (int k = 0; k < 3; k++) {
+        A.lo[k] = sp.lo[k];
+        A.inv[k] = (float)((double)sp.dims[k] / ((double)sp.hi[k] - (double)sp.lo[k]));   // the header's inv_k: formed once, here, and reported
+        A.D[k] = sp.dims[k];
+    }
+    A.channels = (int)Cn; A.f32 = sp.dtype == LCR_STACK_FLOAT32;
+    const char *lds = getenv("LCR_VOXEL_LDS");
+    A.lds = lds && !strcmp(lds, "big") ? LCR_VOXEL_LDS_BIG : lds && !strcmp(lds, "slab") ? LCR_VOXEL_LDS_SLAB : LCR_VOXEL_LDS_AUTO;
+    A.out = base + o_vox;
+    A.source = sp.source ? (int *)(base + o_src) : nullptr;
+    A.count = (int *)(base + o_cnt);
+    A.occupied = (int *)(base + o_occ);
+    A.pose = (float *)(base + o_pose);
+    A.mount = s->wrist.mount;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    s->voxel = A;
+    if (!rc) rc = launch_voxel(s, s->dev, s->stream, nullptr);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->voxel = LcrVoxel{}; return fail(LCR_ERR_UNSUPPORTED, "the voxel-grid kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0], (double)A.inv[1], (double)A.inv[2]); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); s->voxel = LcrVoxel{}; return fail(LCR_ERR_HIP, "making the voxel grid failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->voxel_mem = mem;
+    s->voxel_spec = sp;
+    s->voxel_bytes_per_env = Cn * V * esize;
+    s->voxel_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_voxel_grid(lcr_sim *s, lcr_voxel_grid_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the grid is made behind the frames, on the second stream after a step: the handle's stream waits for it here)
+    memset(out, 0, sizeof *out);
+    if (!s->voxel_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->voxel_spec;
+    for (int k = 0; k < 3; k++) out->inv_cell[k] = s->voxel.inv[k];
+    out->channels = s->voxel.channels;
+    out->slots = s->voxel.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->voxels = s->voxel.out;
+    out->source = s->voxel.source;
+    out->count = s->voxel.count;
+    out->occupied = s->voxel.occupied;
+    out->camera_pose = s->voxel.pose;
+    out->bytes_per_env = (uint64_t)s->voxel_bytes_per_env;
+    return LCR_OK;
 }
 
 int lcr_calibrate_copy(lcr_sim *s, float *dst_dev, size_t n_floats) {

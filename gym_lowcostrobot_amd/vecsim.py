@@ -96,6 +96,7 @@ class VecSim:
         wrist_camera=None,
         obs_stack=None,
         point_cloud=None,
+        voxel_grid=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -167,6 +168,18 @@ class VecSim:
             check(self.L.lcr_point_cloud_sampling_check(ctypes.byref(point_cloud), ctypes.byref(cloud_sampling)))
             if cloud_crop is not None:
                 check(self.L.lcr_point_cloud_crop_check(ctypes.byref(cloud_crop)))
+        # the voxel grid (lcr_enable_voxel_grid): None = none, or a dict of box=((x0, y0, z0), (x1, y1, z1)) and dims=(Dx, Dy, Dz) -- no defaults: the caller chooses the memory --
+        # and some of cameras / ids / features ("occupancy", "rgb") / dtype ("uint8" | "float32") / source.  Checked here and by the library without a handle
+        # (lcr_voxel_grid_check), before it is asked for a device.  It is made of both planes: they are not switched on silently
+        if voxel_grid is not None:
+            if observation_mode == "state":
+                raise ValueError("voxel_grid needs image observations: observation_mode 'image' or 'both'")
+            voxel_grid = _capi.VoxelGridSpec.from_any(voxel_grid)
+            if voxel_grid.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("voxel_grid: cameras selects 'wrist', but no wrist_camera is given")
+            if set(image_planes) != set(_capi.IMAGE_PLANES):
+                raise ValueError(f"voxel_grid is made of the depth and the segmentation plane: pass both, image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_voxel_grid_check(ctypes.byref(voxel_grid)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -348,6 +361,24 @@ class VecSim:
             self.point_cloud_count = DeviceArray(self, cv.count, (N,), np.int32)
             self.point_cloud_source = DeviceArray(self, cv.source, (N, P), np.int32)
             self.point_cloud_pose = DeviceArray(self, cv.camera_pose, (int(cv.slots), 13, N), np.float32)
+        # the voxel grid: (N, C, Dz, Dy, Dx) of its element type, the input of a Conv3d as it stands
+        self.voxel_grid = self.voxel_grid_source = self.voxel_grid_count = self.voxel_grid_occupied = self.voxel_grid_pose = self.voxel_grid_spec = None
+        if voxel_grid is not None:   # (behind look, wrist camera and planes; independent of the stack and the cloud)
+            try:
+                check(self.L.lcr_enable_voxel_grid(self.handle, ctypes.byref(voxel_grid)))
+                vv = _capi.LcrVoxelGridView()
+                check(self.L.lcr_get_voxel_grid(self.handle, ctypes.byref(vv)))
+            except Exception:
+                self.close()
+                raise
+            # (lo, hi and inv_cell: the float32 values in use -- inv_cell is what the kernel multiplies with, the authority for which cell a point falls in)
+            self.voxel_grid_spec = dict(vv.spec.as_dict(), inv_cell=tuple(float(x) for x in vv.inv_cell))
+            Dx, Dy, Dz = self.voxel_grid_spec["dims"]
+            self.voxel_grid = DeviceArray(self, vv.voxels, (N, int(vv.channels), Dz, Dy, Dx), np.dtype(self.voxel_grid_spec["dtype"]))
+            self.voxel_grid_source = DeviceArray(self, vv.source, (N, Dz, Dy, Dx), np.int32) if vv.source else None
+            self.voxel_grid_count = DeviceArray(self, vv.count, (N,), np.int32)
+            self.voxel_grid_occupied = DeviceArray(self, vv.occupied, (N,), np.int32)
+            self.voxel_grid_pose = DeviceArray(self, vv.camera_pose, (int(vv.slots), 13, N), np.float32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -386,7 +417,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack, point cloud): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud, voxel grid): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -620,6 +651,8 @@ class VecSim:
                 obs["image_stack"] = self.obs_stack.numpy()
             if self.point_cloud is not None:
                 obs["point_cloud"] = self.point_cloud.numpy()
+            if self.voxel_grid is not None:
+                obs["voxel_grid"] = self.voxel_grid.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

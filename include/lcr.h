@@ -699,6 +699,81 @@ int lcr_get_point_cloud_crop(lcr_sim *sim, int32_t *enabled, lcr_point_cloud_cro
  *               LAST lcr_step).  A handle without a point cloud is refused (LCR_ERR_INVALID).  count = 0 is LCR_OK.  Nothing of the live cloud is touched. */
 int lcr_point_cloud_terminal(lcr_sim *sim, const int32_t *env_ids_host, int count, float *points_host, int32_t *count_host, int32_t *source_host, float *pose_host);
 
+/* == The voxel grid: an optional device buffer per handle, `voxels` [N][C][Dz][Dy][Dx], that the library keeps current behind the frame kernels -- occupancy (and colour) over a
+ * fixed axis-aligned box of the WORLD frame, fused over the cameras: the dense input of a voxel policy (PerAct, C2F-ARM, 3-D conv encoders), fed straight to a Conv3d as
+ * (N, C, D, H, W).  It is made of ALL candidate pixels, not of the P a point cloud keeps, by one streaming kernel, in stream order, without a host round trip.  Off by
+ * default: without lcr_enable_voxel_grid no byte, state, output or kernel of the handle changes.
+ *   inputs      those of the point cloud: the image observations at the configured size, both planes, the selected camera slots (`cameras`: LCR_STACK_CAM_* bits, 0 = every
+ *               camera the handle has; slots in the order front, top, wrist; the wrist bit on a handle without a wrist camera is refused), `ids` (a mask over the ids 1 .. 10,
+ *               0 = 0x7FC, bit 0 and bits above 10 refused), the cameras of the handle or of the env's look variant, the wrist pose from the pose snapshot.
+ *   candidate   a pixel that is a candidate by the id rule of the point cloud (id = byte & 0x7f, bit `id` set in `ids`; the marker bit 7 is ignored).
+ *   pixel index g = slot H W + row W + px: the global pixel index, the `source` numbering of the cloud.
+ *   point       the pinned chain of "The point cloud inside a crop box", word for word: hx = (float)px + 0.5f - 0.5f * (float)W;  sx = hx * s, one rounded float32 multiply;
+ *               hy = (float)row + 0.5f - 0.5f * (float)H;  sy = - (hy * s);  per axis k:  d_k = fmaf(sx, X_k, fmaf(sy, Y_k, - Z_k)),  p_k = fmaf(t, d_k, ro_k) -- with t the
+ *               float32 depth plane value and ro, X, Y, Z, s the float32 values the kernel writes to a camera_pose buffer of the grid's own, [slots][13][N].  Nothing is
+ *               re-associated or contracted beyond the fmaf named, denormals are kept.
+ *   box, cells  lo[3], hi[3]: float32, FINITE, lo_k < hi_k -- unlike the crop box there are no open sides.  dims = (Dx, Dy, Dz), each in 1 .. 64, Dx a multiple of 4,
+ *               V = Dx Dy Dz <= LCR_VOXEL_MAX_CELLS (32 768).  The library forms inv_k = (float)((double)D_k / ((double)hi_k - (double)lo_k)) once, on the host, and REPORTS
+ *               the three float32 values in the view (inv_cell): the reported values are the authority for everything below.
+ *   voxel       of a candidate, per axis k:  u_k = p_k - lo_k, one float32 subtraction;  v_k = u_k * inv_k, one rounded float32 multiply.  The candidate is inside iff
+ *               u_k >= 0.0f && v_k < (float)D_k on all three axes (u = - 0.0 is inside, in cell 0); then i_k = (int)v_k.  Both operations are opaque to the optimiser.  The
+ *               box is half-open UP TO THIS ROUNDING: a point a rounding below hi_k whose v_k rounds to D_k is outside, and no face of hi is promised either way.
+ *   grid        voxel (ix, iy, iz) is OCCUPIED iff some candidate falls in it; its SOURCE is the smallest g among them -- front wins over top over wrist, then row-major.  An
+ *               order-independent minimum: the grid is deterministic whatever the order lanes arrive in.
+ *   voxels      [N][C][Dz][Dy][Dx]: z is the depth axis, y the height, x the width of a Conv3d input.  Channel 0: occupancy, source byte 255 or 0.  With LCR_VOXEL_RGB in
+ *               `features`: channels 1 .. 3, the colour-frame bytes of the source pixel, 0 where empty.  Elements: LCR_STACK_UINT8 the source byte x, LCR_STACK_FLOAT32
+ *               (float)x * (1.0f / 255.0f), the stack's element rule, bit for bit (LCR_STACK_FLOAT16 is refused).
+ *   source      optional (`source` = 1), [N][Dz][Dy][Dx] int32: the voxel's source g, - 1 where empty.  Off by default: it is 4 V bytes per env.
+ *   count       [N] int32, always: candidates inside the grid.        occupied  [N] int32, always: occupied voxels.
+ *   camera_pose [slots][13][N] float32, always: ro, X, Y, Z, s of every slot per env as the kernel used them, as the cloud reports them.
+ *   invariant   after every entry point that draws the batched frames -- lcr_step, lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- the grid is the
+ *               function above of that env's current frames, planes and cameras.  No history and no reset rule: an auto-reset env shows its reset state, as its frames do.
+ *   ordering    the grid kernel runs behind the frame kernels, the stack kernel and the cloud kernel, on whatever stream they ran on; the event the joining entry points wait
+ *               for is recorded after it.  After a step on the second stream it reads the look snapshot and the pose snapshot the frames used.
+ *   life        needs image observations and BOTH planes; independent of the point cloud: either, both or neither.  Fixed for the life of the handle: the same spec again
+ *               does nothing, another spec is refused, naming both.
+ *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, voxels, the same guard from the first 256-byte boundary at or behind their end (as the
+ *               cloud and the stack have them), then source, count, occupied and camera_pose.  Freed by lcr_destroy; LCR_ERR_OOM if it fails.  N V C sizeof(element) grows
+ *               fast: 32 768 envs of 32 x 32 x 32 with colours are 4 GiB as uint8 and 16 GiB as float32, and `source` adds 4 GiB.
+ *   not in it   mean colours and per-voxel counts, oriented or per-env boxes, float16, the recorder, and the grid of an episode that has ended: there is no _terminal call, so
+ *               the vector adapters refuse the grid.
+ * LCR_VOXEL_LDS=slab|big in the environment (read by lcr_enable_voxel_grid): how the kernel holds a grid of more than 16 384 voxels, a word a voxel in LDS -- in passes over
+ * the planes of one z-slab each (the default), or whole, in a build with 128 KiB of LDS; the same bytes under both (an A/B switch: profiles/voxel_grid.txt). */
+enum { LCR_VOXEL_OCCUPANCY = 1, LCR_VOXEL_RGB = 2 };
+#define LCR_VOXEL_MAX_DIM 64
+#define LCR_VOXEL_MAX_CELLS 32768
+typedef struct lcr_voxel_grid_spec {
+    float lo[3];          /* x, y, z of the box's lower corner, world frame; finite */
+    float hi[3];          /* x, y, z of the upper corner; finite, lo[k] < hi[k] */
+    int32_t dims[3];      /* Dx, Dy, Dz: each 1 .. LCR_VOXEL_MAX_DIM, Dx a multiple of 4, Dx Dy Dz <= LCR_VOXEL_MAX_CELLS */
+    uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+    uint32_t ids;         /* bit i: surface id i is a candidate, i = 1 .. 10; 0 = 0x7FC (arm and cubes) */
+    uint32_t features;    /* LCR_VOXEL_* bits; occupancy is implied, 0 = occupancy only */
+    int32_t dtype;        /* LCR_STACK_UINT8 or LCR_STACK_FLOAT32 */
+    int32_t source;       /* 0 | 1: keep the source index of every voxel */
+} lcr_voxel_grid_spec;
+typedef struct lcr_voxel_grid_view {
+    int32_t enabled;                   /* 0: no grid, everything below is 0 / NULL */
+    lcr_voxel_grid_spec spec;          /* as enabled: `cameras` and `ids` resolved to the bits in use, the occupancy bit set in `features` */
+    float inv_cell[3];                 /* inv_k: cells per metre along x, y, z, the float32 values the kernel multiplies with */
+    int32_t channels, slots, image_width, image_height;
+    const void *voxels;                /* device, [N][C][Dz][Dy][Dx] of the element type */
+    const int32_t *source;             /* device, [N][Dz][Dy][Dx], or NULL */
+    const int32_t *count;              /* device, [N] */
+    const int32_t *occupied;           /* device, [N] */
+    const float *camera_pose;          /* device, [slots][13][N] */
+    uint64_t bytes_per_env;            /* C Dz Dy Dx sizeof(element) */
+} lcr_voxel_grid_view;
+/* The checks lcr_enable_voxel_grid makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field and the axis in the message -- a
+ * corner that is NaN or an infinity, lo_k >= hi_k, a dim outside 1 .. 64, Dx not a multiple of 4, more than LCR_VOXEL_MAX_CELLS voxels, unknown feature bits, a dtype
+ * other than uint8 / float32, source other than 0 / 1, and the cloud's refusals of `cameras` and `ids` */
+int lcr_voxel_grid_check(const lcr_voxel_grid_spec *spec);
+/* Switch the grid on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without both planes and a wrist bit without a wrist camera are
+ * refused (LCR_ERR_INVALID, naming what is missing); an allocation that fails is LCR_ERR_OOM.  Makes the grid of the current frames. */
+int lcr_enable_voxel_grid(lcr_sim *sim, const lcr_voxel_grid_spec *spec);
+/* The grid; waits (on the handle's stream) for frames and grid still being made on the second stream, as every entry point but the step does. */
+int lcr_get_voxel_grid(lcr_sim *sim, lcr_voxel_grid_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */
