@@ -72,8 +72,8 @@ struct LcrDev {
     int newton_iters, ls_iters;      // most Newton iterations per substep / most evaluations of phi' per line search
     float newton_tol, ls_tol;
     int coop_max;                    // Newton kernels: a wave solves up to this many coupled (arm on cube, cube on cube) envs one by one with all its lanes (lcr_newton_coop.h); more: the 12-dimensional SIMT solve
-    int coop_share;                  // one-cube Newton kernel: who solves a wave's coupled envs -- 0 the owning wave only, 1 any wave of the workgroup, the owner first (default),
-                                     // 2 never the owner (lcr_config.coop_share - 1; lcr_kernels.hip: CoopQueue)
+    int coop_share;                  // one-cube Newton kernel: who solves a wave's coupled envs -- 0 the owning wave only, 1 any wave of the workgroup, the owner first,
+                                     // 2 never the owner, 3 as 1 and waves without a coupled env help the waves behind them mid-step (default) (lcr_config.coop_share - 1; lcr_kernels.hip: CoopQueue)
     int img_w, img_h;                // size of the image observations (lcr_config.image_width / image_height; 320 x 240 by default)
     int img_epw;                     // frame kernel: envs per workgroup (1, 2 or 4), chosen from the frame size at lcr_create (lcr_render.hip)
 };

@@ -12,11 +12,12 @@ from gym_lowcostrobot_amd import VecSim  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("tasks", nargs="*", default=["reach", "push", "lift", "pick_place_ee", "stack", "push_loop"])
 ap.add_argument("--n", type=int, default=65536)
+ap.add_argument("--coop-share", default=None, choices=["owner", "shared", "handoff", "ahead"])   # (None: the library's default)
 a = ap.parse_args()
 for name in a.tasks:
     mode = "ee" if name.endswith("_ee") else "joint"
     task = name.replace("_ee", "")
-    sim = VecSim(task, a.n, action_mode=mode, profile="wave_cycles")
+    sim = VecSim(task, a.n, action_mode=mode, profile="wave_cycles", coop_share=a.coop_share)
     bufs = [sim.alloc_actions() for _ in range(16)]
     for i, b in enumerate(bufs):
         sim.fill_random_actions(b, 0, i)
@@ -29,8 +30,8 @@ for name in a.tasks:
         tot, solve, cpl, ch = (x.numpy()[::64].astype(np.float64) for x in (sim.max_sweeps, sim.active_mask, sim.active_count, sim.choice))
         # (one-cube Newton kernel, four-wave workgroups: lane 1 of active_count = cycles spent on other waves' patients, lane 2 = own patients other waves solved)
         ac = sim.active_count.numpy().astype(np.float64)
-        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0), ac[1::64], ac[2::64]))
-    tot, solve, cpl, ncpl, its, nslow, helpc, handed = (np.stack([r[k] for r in rows]) for k in range(8))   # [step][wave]
+        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0), ac[1::64], ac[2::64], ac[3::64]))
+    tot, solve, cpl, ncpl, its, nslow, helpc, handed, ahead = (np.stack([r[k] for r in rows]) for k in range(9))   # [step][wave]
     slow = tot.argmax(1)
     pick = lambda x: x[np.arange(len(slow)), slow].mean()
     print(f"{name:14s} n={a.n}: cycles per control step and wave, MEAN wave | SLOWEST wave of the step (mean over 20 steps)")
@@ -44,5 +45,16 @@ for name in a.tasks:
     if task != "stack" and task != "push_loop":
         print(f"   cooperative cycles left on the owner's path (coupled solves above); cycles helping other waves {helpc.mean():10.0f} | {pick(helpc):10.0f};"
               f" own patients handed off {handed.mean():.2f} | {pick(handed):.2f} of {ncpl.mean():.2f} | {pick(ncpl):.2f}")
+        # what handing off can still win: the launch cannot end before the wave with the most cycles OUTSIDE its own-path cooperative passes
+        at = lambda q: np.abs(tot - np.percentile(tot, q, axis=1, keepdims=True)).argmin(1)   # per step: the wave at that percentile of the totals
+        w99, w90 = at(99), at(90)
+        rest = (tot - cpl).max(1).mean()
+        print(f"   own-path cooperative cycles of the slowest | p99 | p90 wave of a step: {pick(cpl):.0f} | {cpl[np.arange(len(w99)), w99].mean():.0f} | {cpl[np.arange(len(w90)), w90].mean():.0f}"
+              f" (their totals {pick(tot):.0f} | {tot[np.arange(len(w99)), w99].mean():.0f} | {tot[np.arange(len(w90)), w90].mean():.0f});"
+              f" largest total - own-path cooperative {rest:.0f}: ceiling {pick(tot) - rest:.0f} = {100 * (pick(tot) - rest) / pick(tot):.1f} % of the slowest wave")
+        hs = helpc[np.arange(len(slow)), slow]
+        print(f"   slowest wave of a step: helping cycles above its own-path cooperative cycles in {100 * (hs > cpl[np.arange(len(slow)), slow]).mean():.0f} % of the steps")
+        if a.coop_share == "ahead":   # (lane 3 carries the counter under that mode only)
+            print(f"   patients solved for waves at an earlier substep while the wave had none of its own: {ahead.mean():.2f} | {pick(ahead):.2f}, most {ahead.max():.0f}; waves with any: {100 * (ahead > 0).mean():.0f} %")
     print(f"   Newton iterations executed by the wave: {its.mean():.1f} | {pick(its):.1f};  cycles per iteration (solves / iterations): {solve.sum() / max(its.sum(), 1):.0f}", flush=True)
     sim.close()
