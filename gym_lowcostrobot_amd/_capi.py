@@ -20,7 +20,7 @@ REWARD_TYPES = {"sparse": 0, "dense": 1}
 STEP_KERNELS = {"auto": 0, "single": 1, "coop": 2}   # lcr_config.step_kernel
 SOLVERS = {"pgs": 0, "newton": 1}                     # lcr_config.solver
 PRESETS = {"faithful": 0, "fast": 1}                  # lcr_config_preset
-COOP_SHARE = {None: 0, "owner": 1, "shared": 2, "handoff": 3, "ahead": 4}   # lcr_config.coop_share (one-cube Newton kernel; bit-identical results; None: "ahead")
+COOP_SHARE = {None: 0, "owner": 1, "shared": 2, "handoff": 3, "ahead": 4, "early": 5}   # lcr_config.coop_share (one-cube Newton kernel; bit-identical results; None: "early")
 PROFILE_MODES = {None: None, "wave_cycles": 2, "phase_cycles": 3}   # lcr_config.diagnostics values 2, 3 (per-wave cycle read-back; see include/lcr.h)
 COMPAT_ZERO_QVEL_ON_RESET = 1
 COMPAT_COLD_SOLVE_EACH_STEP = 2   # contact solver starts every control step from zero forces (default: forces carried across steps)

@@ -445,7 +445,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
     if (cfg->pgs_iters < 0 && !(cfg->pgs_tol > 0)) return fail(LCR_ERR_INVALID, "pgs_tol must be positive in converged mode (pgs_iters < 0)");
     if (cfg->finger_cube_condim != 0 && cfg->finger_cube_condim != 4 && cfg->finger_cube_condim != 6) return fail(LCR_ERR_INVALID, "finger_cube_condim must be 4 or 6");
     if (cfg->cc_points != 0 && cfg->cc_points != 4 && cfg->cc_points != 8) return fail(LCR_ERR_INVALID, "cc_points must be 4 or 8");
-    if (cfg->coop_share < 0 || cfg->coop_share > 4) return fail(LCR_ERR_INVALID, "coop_share must be 0 (default), 1 (owner only), 2 (shared), 3 (always hand off) or 4 (ahead)");
+    if (cfg->coop_share < 0 || cfg->coop_share > 5) return fail(LCR_ERR_INVALID, "coop_share must be 0 (default), 1 (owner only), 2 (shared), 3 (always hand off), 4 (ahead) or 5 (early)");
     // frame size: both zero (320 x 240) or each a multiple of 4 in [16, 512] (lcr.h: 16-byte aligned bands, one 32-bit mask of tile columns); checked whatever obs_mode is
     if ((cfg->image_width == 0) != (cfg->image_height == 0)) return fail(LCR_ERR_INVALID, "image_width and image_height must both be 0 (320 x 240) or both be set (got %d x %d)", cfg->image_width, cfg->image_height);
     if (cfg->image_width != 0 && (cfg->image_width < 16 || cfg->image_width > 512 || cfg->image_width % 4 != 0)) return fail(LCR_ERR_INVALID, "image_width must be a multiple of 4 in [16, 512] (got %d)", cfg->image_width);
@@ -650,7 +650,7 @@ int lcr_create(const lcr_config *cfg, lcr_sim **out) {
             D.newton = cfg->solver == LCR_SOLVER_NEWTON ? 1 : 0;
             D.newton_iters = cfg->newton_iters; D.ls_iters = cfg->ls_iters;
             D.newton_tol = (float)cfg->newton_tol; D.ls_tol = (float)cfg->ls_tol;
-            D.coop_share = cfg->coop_share == 0 ? 3 : cfg->coop_share - 1;   // (one-cube Newton kernel: who solves a wave's coupled envs; the bits do not depend on it.  Default: ahead)
+            D.coop_share = cfg->coop_share == 0 ? 4 : cfg->coop_share - 1;   // (one-cube Newton kernel: who solves a wave's coupled envs; the bits do not depend on it.  Default: early)
             // coupled envs a wave of the Newton kernels solves cooperatively (lcr_newton_coop.h: four per pass, one per 16-lane row; StackTwoCubes' three-body patients one at a time)
             // before it falls back to the coupled SIMT solves: 8 with one cube (two passes; flat beyond), 16 with rails and for Stack (PushCubeLoop 5.52 / 4.91 / 4.90 ms at 4 / 8 / 16: the
             // fall-back's 12-dim SIMT iteration spills; Stack's 18-dim one 3 KB per lane: profiles/r06_coop_sweep.txt, r06_coop_sweep2.txt); measurement override: LCR_COOP_MAX (0: never)

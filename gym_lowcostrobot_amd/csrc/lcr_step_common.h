@@ -526,7 +526,7 @@ DEV SBHit pad_box(f3 pc, f3 PX, f3 PY, f3 PZ, f3 ph, f3 cp, const CubeRot &R) {
 // per-env diagnostics of one control step (written only when LcrDev.diag): which constraint slots were active (bit = slot id:
 // 0-7 floor<->cube, 8-11 cube<->cube / rails, 12-13 finger<->cube, 14-15 finger<->floor, 16 arm-link proxies, 18+j limit j),
 // the number of (slot, substep) activations, and the largest PGS sweep count of a substep
-struct Diag { unsigned mask, count, sweeps, choice, help = 0u, handed = 0u, ahead = 0u; };   // (help / handed / ahead: diagnostics = 2 counters of the one-cube Newton kernel's queue)
+struct Diag { unsigned mask, count, sweeps, choice, help = 0u, handed = 0u, ahead = 0u, early = 0u, wait = 0u; };   // (help / handed / ahead / early / wait: diagnostics = 2 counters of the one-cube Newton kernel's queue)
 // choice: wrapping sum over substeps s (weight 2s + 1) and active constraints of (slot + 1)(sel + 1) 2654435761, sel = the discrete choice behind
 // the contact (vertex index, manifold candidate, box face case, proxy member, limit side) -- same formula as the oracle's
 DEV void diag_choice(Diag &DG, bool act, int slot, int sel) { DG.choice += act ? (unsigned)(slot + 1) * (unsigned)(sel + 1) * 2654435761u : 0u; }

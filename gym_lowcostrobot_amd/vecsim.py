@@ -239,8 +239,8 @@ class VecSim:
             cfg.global_envs = int(global_envs)
         if cc_points is not None:   # StackTwoCubes: 4 (default) or 8 cube<->cube manifold points
             cfg.cc_points = int(cc_points)
-        if coop_share not in _capi.COOP_SHARE:   # one-cube Newton kernel: who solves a wave's coupled envs (None = the library's default; "owner" | "shared" | "handoff" | "ahead": A/B runs, bit-identical)
-            raise ValueError(f"invalid coop_share {coop_share!r} (None | 'owner' | 'shared' | 'handoff' | 'ahead')")
+        if coop_share not in _capi.COOP_SHARE:   # one-cube Newton kernel: who solves a wave's coupled envs (None = the library's default; "owner" | "shared" | "handoff" | "ahead" | "early": A/B runs, bit-identical)
+            raise ValueError(f"invalid coop_share {coop_share!r} (None | 'owner' | 'shared' | 'handoff' | 'ahead' | 'early')")
         cfg.coop_share = _capi.COOP_SHARE[coop_share]
         if image_size is not None:   # (height, width) of the image observations, numpy order as the arrays are (N, H, W, 3); None = 240 x 320.  The library checks the values
             try:

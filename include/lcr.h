@@ -139,8 +139,9 @@ typedef struct lcr_config {
     int32_t coop_share;        /* LCR_SOLVER_NEWTON, one-cube tasks: who solves the coupled envs of a wave (arm on its cube; four per pass with the whole wave).  The kernel runs
                                   four waves per workgroup; a wave stages its coupled envs into a queue in LDS before its small solves, and 2 = shared: any wave of the
                                   workgroup claims them, the owner its own first, and a wave that has finished its step keeps serving the queue; 1 = owner only; 3 = always hand
-                                  off (another wave solves them: tests); 4 = ahead (0 = default): shared, and a wave that has no coupled env in a substep makes one pass over the queued envs of waves
-                                  that are at an earlier substep.  A/B switch only: the results are bit-identical under all four.  Other values: LCR_ERR_INVALID */
+                                  off (another wave solves them: tests); 4 = ahead: shared, and a wave that has no coupled env in a substep makes one pass over the queued envs of waves
+                                  that are at an earlier substep; 5 = early (0 = default): ahead, and every wave, coupled envs of its own or not, makes such a pass before its small
+                                  solves, between them and when its own coupled envs are solved as well.  A/B switch only: the results are bit-identical under all five.  Other values: LCR_ERR_INVALID */
     /* ABI v7 */
     int32_t image_width;       /* image_width x image_height: size of the image observations (observation_mode image / both; checked whatever the mode).  0, 0 = LCR_IMG_W x LCR_IMG_H (320 x 240, the
                                   reference's).  Otherwise each a multiple of 4 in [16, 512]: a band of 4 rows is 12 W bytes, a multiple of 16 exactly when W % 4 == 0, so every

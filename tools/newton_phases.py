@@ -12,7 +12,7 @@ from gym_lowcostrobot_amd import VecSim  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("tasks", nargs="*", default=["reach", "push", "lift", "pick_place_ee", "stack", "push_loop"])
 ap.add_argument("--n", type=int, default=65536)
-ap.add_argument("--coop-share", default=None, choices=["owner", "shared", "handoff", "ahead"])   # (None: the library's default)
+ap.add_argument("--coop-share", default=None, choices=["owner", "shared", "handoff", "ahead", "early"])   # (None: the library's default)
 a = ap.parse_args()
 for name in a.tasks:
     mode = "ee" if name.endswith("_ee") else "joint"
@@ -30,8 +30,8 @@ for name in a.tasks:
         tot, solve, cpl, ch = (x.numpy()[::64].astype(np.float64) for x in (sim.max_sweeps, sim.active_mask, sim.active_count, sim.choice))
         # (one-cube Newton kernel, four-wave workgroups: lane 1 of active_count = cycles spent on other waves' patients, lane 2 = own patients other waves solved)
         ac = sim.active_count.numpy().astype(np.float64)
-        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0), ac[1::64], ac[2::64], ac[3::64]))
-    tot, solve, cpl, ncpl, its, nslow, helpc, handed, ahead = (np.stack([r[k] for r in rows]) for k in range(9))   # [step][wave]
+        rows.append((tot, solve, cpl, np.mod(np.floor(ch / 65536.0), 256.0), np.mod(ch, 65536.0), np.floor(ch / 16777216.0), ac[1::64], ac[2::64], ac[3::64], ac[4::64], ac[5::64]))
+    tot, solve, cpl, ncpl, its, nslow, helpc, handed, ahead, early, wait = (np.stack([r[k] for r in rows]) for k in range(11))   # [step][wave]
     slow = tot.argmax(1)
     pick = lambda x: x[np.arange(len(slow)), slow].mean()
     print(f"{name:14s} n={a.n}: cycles per control step and wave, MEAN wave | SLOWEST wave of the step (mean over 20 steps)")
@@ -54,7 +54,12 @@ for name in a.tasks:
               f" largest total - own-path cooperative {rest:.0f}: ceiling {pick(tot) - rest:.0f} = {100 * (pick(tot) - rest) / pick(tot):.1f} % of the slowest wave")
         hs = helpc[np.arange(len(slow)), slow]
         print(f"   slowest wave of a step: helping cycles above its own-path cooperative cycles in {100 * (hs > cpl[np.arange(len(slow)), slow]).mean():.0f} % of the steps")
-        if a.coop_share == "ahead":   # (lane 3 carries the counter under that mode only)
+        # (lane 5) what an earlier claim by the helpers can remove: the slowest wave's own-path cooperative cycles after the last pass in which it solved a patient of its own
+        print(f"   own-path cooperative cycles after the wave's last pass over patients of its own (waiting for the waves that hold the rest): {wait.mean():.0f} | {pick(wait):.0f}"
+              f" = {100 * pick(wait) / max(pick(cpl), 1):.0f} % of the slowest wave's own-path cooperative cycles, {100 * pick(wait) / pick(tot):.1f} % of its total")
+        if a.coop_share in (None, "early"):   # (lane 4 carries the counter under that mode only)
+            print(f"   patients solved for waves at an earlier substep at the claim points before / between the small solves and after the wave's own patients: {early.mean():.2f} | {pick(early):.2f}, most {early.max():.0f}; waves with any: {100 * (early > 0).mean():.0f} %")
+        if a.coop_share in (None, "ahead", "early"):   # (lane 3 carries the counter under these modes only)
             print(f"   patients solved for waves at an earlier substep while the wave had none of its own: {ahead.mean():.2f} | {pick(ahead):.2f}, most {ahead.max():.0f}; waves with any: {100 * (ahead > 0).mean():.0f} %")
     print(f"   Newton iterations executed by the wave: {its.mean():.1f} | {pick(its):.1f};  cycles per iteration (solves / iterations): {solve.sum() / max(its.sum(), 1):.0f}", flush=True)
     sim.close()

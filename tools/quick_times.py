@@ -23,7 +23,7 @@ ap.add_argument("--newton-tol", type=float, default=None)
 ap.add_argument("--ls-tol", type=float, default=None)
 ap.add_argument("--finger-cube-condim", type=int, default=None)
 ap.add_argument("--cc-points", type=int, default=None)
-ap.add_argument("--coop-share", default=None, choices=["owner", "shared", "handoff", "ahead"])   # (one-cube Newton kernels; None: the library's default)
+ap.add_argument("--coop-share", default=None, choices=["owner", "shared", "handoff", "ahead", "early"])   # (one-cube Newton kernels; None: the library's default)
 a = ap.parse_args()
 for name in a.names:
     task, mode = W[name]
