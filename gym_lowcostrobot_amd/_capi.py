@@ -45,6 +45,9 @@ CLOUD_MAX_POOL = 4096                       # LCR_CLOUD_MAX_POOL
 # the voxel grid (lcr_enable_voxel_grid): LCR_VOXEL_* feature bits, LCR_VOXEL_MAX_DIM, LCR_VOXEL_MAX_CELLS; its cameras, ids and dtypes are the cloud's and the stack's
 VOXEL_FEATURES = {"occupancy": 1, "rgb": 2}
 VOXEL_MAX_DIM, VOXEL_MAX_CELLS = 64, 32768
+# the heightmap (lcr_enable_heightmap): LCR_HEIGHTMAP_* feature bits, LCR_HEIGHTMAP_MAX_DIM, LCR_HEIGHTMAP_MAX_CELLS; its cameras and ids are the cloud's
+HEIGHTMAP_FEATURES = {"height": 1, "rgb": 2}
+HEIGHTMAP_MAX_DIM, HEIGHTMAP_MAX_CELLS = 256, 16384
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -65,6 +68,7 @@ SYMBOLS = [
     "lcr_point_cloud_crop_check", "lcr_enable_point_cloud_cropped", "lcr_get_point_cloud_crop",
     "lcr_enable_obs_stack_terminal", "lcr_get_obs_stack_terminal", "lcr_obs_stack_terminal", "lcr_point_cloud_terminal",
     "lcr_voxel_grid_check", "lcr_enable_voxel_grid", "lcr_get_voxel_grid",
+    "lcr_heightmap_check", "lcr_enable_heightmap", "lcr_get_heightmap",
 ]
 
 
@@ -620,6 +624,120 @@ class LcrVoxelGridView(ctypes.Structure):
     ]
 
 
+class HeightmapSpec(ctypes.Structure):
+    """lcr_heightmap_spec: box, cells, cameras, surface ids and channels of the heightmap (include/lcr.h)"""
+    _fields_ = [
+        ("lo", ctypes.c_float * 3),      # x, y, z of the box's lower corner, world frame; finite
+        ("hi", ctypes.c_float * 3),      # x, y, z of the upper corner; finite, lo[k] < hi[k]
+        ("dims", ctypes.c_int32 * 2),    # Hx (a multiple of 4), Hy: each 1 .. HEIGHTMAP_MAX_DIM, at most HEIGHTMAP_MAX_CELLS cells
+        ("cameras", ctypes.c_uint32),    # STACK_CAMERAS bits; 0 = every camera the handle has
+        ("ids", ctypes.c_uint32),        # bit i: surface id i is a candidate (1 .. 10); 0 = CLOUD_DEFAULT_IDS
+        ("features", ctypes.c_uint32),   # HEIGHTMAP_FEATURES bits; the height is implied
+        ("source", ctypes.c_int32),      # 0 | 1: keep the source index of every cell
+    ]
+
+    def as_dict(self):
+        """the float32 corners in use as Python floats, cameras / features as names, ids as a tuple, as VoxelGridSpec.as_dict has them"""
+        return {"lo": tuple(float(v) for v in self.lo), "hi": tuple(float(v) for v in self.hi), "dims": tuple(int(v) for v in self.dims),
+                "cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b), "ids": tuple(i for i in range(32) if self.ids >> i & 1),
+                "features": tuple(n for n, b in HEIGHTMAP_FEATURES.items() if self.features & b), "source": bool(self.source)}
+
+    @classmethod
+    def from_any(cls, v):
+        """a HeightmapSpec, or a dict with box=((x0, y0, z0), (x1, y1, z1)) and dims=(Hx, Hy) -- neither has a default: the caller chooses the memory -- and some of
+        cameras / ids / features / source"""
+        import numpy as np
+
+        if isinstance(v, cls):
+            return v
+        if not isinstance(v, dict):
+            raise ValueError(f"heightmap must be None or a dict of box / dims / cameras / ids / features / source, got {v!r}")
+        v = dict(v)
+        out = cls()
+        if "box" not in v or "dims" not in v:
+            raise ValueError("heightmap needs box=((x0, y0, z0), (x1, y1, z1)) and dims=(Hx, Hy): neither has a default, the caller chooses the memory")
+        box, dims = v.pop("box"), v.pop("dims")
+        what = "heightmap: box must be ((x0, y0, z0), (x1, y1, z1)), the lower and the upper corner of a box in the world frame, six finite numbers"
+        try:
+            lo, hi = box
+            lo, hi = list(lo), list(hi)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}, got {box!r}") from None
+        if isinstance(box, str) or len(lo) != 3 or len(hi) != 3:
+            raise ValueError(f"{what}, got {box!r}")
+        for name, side, dst in (("lo", lo, out.lo), ("hi", hi, out.hi)):
+            for k, x in enumerate(side):
+                if isinstance(x, (bool, np.bool_, str)) or not isinstance(x, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"{what}; {name}[{k}] is {x!r}")
+                x = np.float32(x)   # (the float32 value the kernel subtracts)
+                if not np.isfinite(x):
+                    raise ValueError(f"heightmap: box {name}[{k}] is not finite: the box of a heightmap has no open sides")
+                dst[k] = float(x)
+        for k, axis in enumerate("xyz"):
+            if not out.lo[k] < out.hi[k]:
+                raise ValueError(f"heightmap: box lo[{k}] >= hi[{k}]: the box is empty along {axis} (lo {out.lo[k]!r}, hi {out.hi[k]!r})")
+        try:
+            dims = list(dims)
+        except TypeError:
+            dims = []
+        if len(dims) != 2 or any(isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, np.integer)) or not 1 <= d <= HEIGHTMAP_MAX_DIM for d in dims):
+            raise ValueError(f"heightmap: dims must be (Hx, Hy), each an integer in 1 .. {HEIGHTMAP_MAX_DIM}, got {dims!r}")
+        if dims[0] % 4:
+            raise ValueError(f"heightmap: dims[0] (x) must be a multiple of 4, got {dims[0]!r}")
+        if dims[0] * dims[1] > HEIGHTMAP_MAX_CELLS:
+            raise ValueError(f"heightmap: dims {tuple(dims)!r} are {dims[0] * dims[1]} cells: at most {HEIGHTMAP_MAX_CELLS}")
+        for k in range(2):
+            out.dims[k] = int(dims[k])
+        cams = v.pop("cameras", None)
+        if cams is not None:
+            if isinstance(cams, str) or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"heightmap: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        ids = v.pop("ids", None)
+        if ids is not None:
+            mask = 0
+            ok = not isinstance(ids, str) and hasattr(ids, "__iter__")
+            for i in (ids if ok else ()):
+                if isinstance(i, str) and i in CLOUD_IDS:
+                    mask |= CLOUD_IDS[i]
+                elif isinstance(i, (int, np.integer)) and not isinstance(i, (bool, np.bool_)) and 1 <= i <= 10:
+                    mask |= 1 << int(i)
+                else:
+                    ok = False
+            if not ok or mask == 0:
+                raise ValueError(f"heightmap: ids must be a non-empty tuple drawn from 'arm', 'cube', 'cube2', 'floor' and the surface ids 1 .. 10, got {ids!r}")
+            out.ids = mask
+        feats = v.pop("features", ("height",))
+        if isinstance(feats, str) or not hasattr(feats, "__iter__") or not all(isinstance(f, str) and f in HEIGHTMAP_FEATURES for f in feats):
+            raise ValueError(f"heightmap: features must be a tuple drawn from 'height' (implied) and 'rgb', got {feats!r}")
+        out.features = HEIGHTMAP_FEATURES["height"] | sum(HEIGHTMAP_FEATURES[f] for f in set(feats))
+        source = v.pop("source", False)
+        if not isinstance(source, (bool, np.bool_)):
+            raise ValueError(f"heightmap: source must be a bool, got {source!r}")
+        out.source = int(source)
+        if v:
+            raise ValueError(f"unknown heightmap fields {sorted(v)}")
+        return out
+
+
+class LcrHeightmapView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", HeightmapSpec),           # cameras and ids resolved to the bits in use, the height bit set
+        ("inv_cell", ctypes.c_float * 2),  # cells per metre along x, y: the float32 values the kernel multiplies with
+        ("channels", ctypes.c_int32),
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("heightmap", ctypes.c_void_p),    # [N][C][Hy][Hx] float32
+        ("source", ctypes.c_void_p),       # [N][Hy][Hx] int32, or NULL
+        ("count", ctypes.c_void_p),        # [N] int32
+        ("filled", ctypes.c_void_p),       # [N] int32
+        ("camera_pose", ctypes.c_void_p),  # [slots][13][N] float32
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -761,6 +879,9 @@ def load():
     L.lcr_voxel_grid_check.argtypes = [ctypes.POINTER(VoxelGridSpec)]
     L.lcr_enable_voxel_grid.argtypes = [vp, ctypes.POINTER(VoxelGridSpec)]
     L.lcr_get_voxel_grid.argtypes = [vp, ctypes.POINTER(LcrVoxelGridView)]
+    L.lcr_heightmap_check.argtypes = [ctypes.POINTER(HeightmapSpec)]
+    L.lcr_enable_heightmap.argtypes = [vp, ctypes.POINTER(HeightmapSpec)]
+    L.lcr_get_heightmap.argtypes = [vp, ctypes.POINTER(LcrHeightmapView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

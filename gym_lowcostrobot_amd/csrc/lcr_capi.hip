@@ -16,6 +16,7 @@
 #include "lcr_stack.h"
 #include "lcr_cloud.h"
 #include "lcr_voxel.h"
+#include "lcr_heightmap.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -198,6 +199,12 @@ struct lcr_sim {
     LcrVoxel voxel;                    // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
     void *voxel_mem;
     size_t voxel_bytes_per_env;
+    // the heightmap (lcr_enable_heightmap): one allocation -- guard, map, guard, source, count, filled, camera poses --, fixed for the life of the handle
+    bool height_on;
+    lcr_heightmap_spec height_spec;    // as enabled, cameras, ids and features resolved
+    LcrHeightmap height;               // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
+    void *height_mem;
+    size_t height_bytes_per_env;
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -262,13 +269,24 @@ static int launch_voxel(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     return lcr_launch_voxel_grid(A, stream);
 }
 
+// the heightmap kernel, behind the frame kernels (the stack, the cloud and the grid kernel) on their stream: the map of P's envs from the frames just drawn, with the cameras
+// that drew them and the wrist pose from P's qpos, as launch_cloud passes them
+static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
+    LcrHeightmap A = s->height;
+    A.front = s->cam_front; A.top = s->cam_top;
+    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
+    A.qpos = P.qpos;
+    return lcr_launch_heightmap(A, stream);
+}
+
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
-// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, and on one with a voxel grid its kernel last
+// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, and on one with a heightmap its kernel last
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
     if (s->cloud_on) LAUNCHCHK("point-cloud kernel", launch_cloud(s, P, stream, look));
     if (s->voxel_on) LAUNCHCHK("voxel-grid kernel", launch_voxel(s, P, stream, look));
+    if (s->height_on) LAUNCHCHK("heightmap kernel", launch_heightmap(s, P, stream, look));
     return LCR_OK;
 }
 
@@ -771,6 +789,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->stack_mem) (void)hipFree(s->stack_mem);
     if (s->cloud_mem) (void)hipFree(s->cloud_mem);
     if (s->voxel_mem) (void)hipFree(s->voxel_mem);
+    if (s->height_mem) (void)hipFree(s->height_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -2126,6 +2145,141 @@ int lcr_get_voxel_grid(lcr_sim *s, lcr_voxel_grid_view *out) {
     out->occupied = s->voxel.occupied;
     out->camera_pose = s->voxel.pose;
     out->bytes_per_env = (uint64_t)s->voxel_bytes_per_env;
+    return LCR_OK;
+}
+
+// ---- the heightmap ----
+
+int lcr_heightmap_check(const lcr_heightmap_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    static const char *const axis = "xyz";
+    // (by the bits, read as an integer from the struct: this unit is built with -ffast-math, under which no test of a float VALUE for NaN or infinity survives)
+    const auto finite = [](const float *v) { uint32_t b; memcpy(&b, v, sizeof b); return (b & 0x7f800000u) != 0x7f800000u; };
+    for (int k = 0; k < 3; k++) {
+        if (!finite(&spec->lo[k])) return fail(LCR_ERR_INVALID, "lo[%d] (%c) is not finite: the box of a heightmap has no open sides", k, axis[k]);
+        if (!finite(&spec->hi[k])) return fail(LCR_ERR_INVALID, "hi[%d] (%c) is not finite: the box of a heightmap has no open sides", k, axis[k]);
+    }
+    for (int k = 0; k < 3; k++)
+        if (!(spec->lo[k] < spec->hi[k]))
+            return fail(LCR_ERR_INVALID, "lo[%d] >= hi[%d]: the box is empty along %c (lo %.9g, hi %.9g)", k, k, axis[k], (double)spec->lo[k], (double)spec->hi[k]);
+    for (int k = 0; k < 2; k++)
+        if (spec->dims[k] < 1 || spec->dims[k] > LCR_HEIGHTMAP_MAX_DIM)
+            return fail(LCR_ERR_INVALID, "dims[%d] (%c) must be in 1 .. %d, got %d", k, axis[k], LCR_HEIGHTMAP_MAX_DIM, spec->dims[k]);
+    if (spec->dims[0] % 4 != 0) return fail(LCR_ERR_INVALID, "dims[0] (x) must be a multiple of 4 (the kernel writes four cells along x at a time), got %d", spec->dims[0]);
+    if ((int64_t)spec->dims[0] * spec->dims[1] > LCR_HEIGHTMAP_MAX_CELLS)
+        return fail(LCR_ERR_INVALID, "dims %d x %d are %lld cells: at most %d", spec->dims[0], spec->dims[1], (long long)spec->dims[0] * spec->dims[1], LCR_HEIGHTMAP_MAX_CELLS);
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be a mask of 1 (front), 2 (top) and 4 (wrist), or 0 for every camera of the handle, got %u", spec->cameras);
+    if (spec->ids & ~(uint32_t)0x7FEu)
+        return fail(LCR_ERR_INVALID, "ids must be a mask over the surface ids 1 .. 10 (bits 1 .. 10; bit 0 is the sky, which is no surface), or 0 for arm and cubes (0x7FC), got 0x%x", spec->ids);
+    if (spec->features & ~(uint32_t)(LCR_HEIGHTMAP_HEIGHT | LCR_HEIGHTMAP_RGB))
+        return fail(LCR_ERR_INVALID, "features must be a mask of 1 (height, implied) and 2 (rgb), got %u", spec->features);
+    if (spec->source != 0 && spec->source != 1) return fail(LCR_ERR_INVALID, "source must be 0 or 1, got %d", spec->source);
+    return LCR_OK;
+}
+
+// "box (x y z) .. (x y z), dims a x b, cameras, ids, features, source" into buf: how the refusal names a spec
+static const char *heightmap_spec_text(char (&buf)[320], const lcr_heightmap_spec &v) {
+    snprintf(buf, sizeof buf, "box (%.9g %.9g %.9g) .. (%.9g %.9g %.9g), dims %d x %d, cameras %u, ids 0x%x, features %u, source %d", (double)v.lo[0], (double)v.lo[1],
+             (double)v.lo[2], (double)v.hi[0], (double)v.hi[1], (double)v.hi[2], v.dims[0], v.dims[1], v.cameras, v.ids, v.features, v.source);
+    return buf;
+}
+
+int lcr_enable_heightmap(lcr_sim *s, const lcr_heightmap_spec *spec) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_heightmap_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a heightmap of");
+    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
+    if ((s->planes & both) != both)
+        return fail(LCR_ERR_INVALID, "the heightmap needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the map): %s",
+                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
+    lcr_heightmap_spec sp = *spec;
+    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
+    sp.features |= LCR_HEIGHTMAP_HEIGHT;
+    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the map)");
+    if (s->height_on) {
+        // (the boxes compare as float32 values: the kernel then forms the same cells; no corner is a NaN)
+        bool same = memcmp(sp.dims, s->height_spec.dims, sizeof sp.dims) == 0 && sp.cameras == s->height_spec.cameras && sp.ids == s->height_spec.ids &&
+                    sp.features == s->height_spec.features && sp.source == s->height_spec.source;
+        for (int k = 0; k < 3 && same; k++) same = sp.lo[k] == s->height_spec.lo[k] && sp.hi[k] == s->height_spec.hi[k];
+        if (same) return LCR_OK;
+        char was[320], asked[320];
+        return fail(LCR_ERR_INVALID, "a heightmap (%s) is enabled already and fixed for the life of the handle: asked for %s", heightmap_spec_text(was, s->height_spec), heightmap_spec_text(asked, sp));
+    }
+    LcrHeightmap A{};
+    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
+        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
+    };
+    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
+    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
+    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    const size_t N = (size_t)s->dev.n, M = (size_t)sp.dims[0] * sp.dims[1], Cn = (sp.features & LCR_HEIGHTMAP_RGB) ? 4 : 1;
+    // guard, map, guard (include/lcr.h: LCR_WRIST_GUARD), then source, count, filled and the camera poses
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_map = C.take(N * Cn * M * sizeof(float));
+    C.skip(LCR_WRIST_GUARD);
+    const size_t guarded = C.off;
+    const size_t o_src = C.take(sp.source ? N * M * sizeof(int) : 0);
+    const size_t o_cnt = C.take(N * sizeof(int));
+    const size_t o_fil = C.take(N * sizeof(int));
+    const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
+    const size_t off = C.off;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the heightmap failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.ids = sp.ids;
+    for (int k = 0; k < 3; k++) A.lo[k] = sp.lo[k];
+    A.hi_z = sp.hi[2];
+    for (int k = 0; k < 2; k++) {
+        A.inv[k] = (float)((double)sp.dims[k] / ((double)sp.hi[k] - (double)sp.lo[k]));   // the header's inv_k: formed once, here, and reported
+        A.D[k] = sp.dims[k];
+    }
+    A.channels = (int)Cn;
+    const char *rounds = getenv("LCR_HEIGHTMAP_ROUNDS");
+    A.rounds = rounds && !strcmp(rounds, "1") ? 1 : rounds && !strcmp(rounds, "4") ? 4 : 0;
+    A.out = (float *)(base + o_map);
+    A.source = sp.source ? (int *)(base + o_src) : nullptr;
+    A.count = (int *)(base + o_cnt);
+    A.filled = (int *)(base + o_fil);
+    A.pose = (float *)(base + o_pose);
+    A.mount = s->wrist.mount;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    s->height = A;
+    if (!rc) rc = launch_heightmap(s, s->dev, s->stream, nullptr);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->height = LcrHeightmap{}; return fail(LCR_ERR_UNSUPPORTED, "the heightmap kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0], (double)A.inv[1]); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); s->height = LcrHeightmap{}; return fail(LCR_ERR_HIP, "making the heightmap failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->height_mem = mem;
+    s->height_spec = sp;
+    s->height_bytes_per_env = Cn * M * sizeof(float);
+    s->height_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_heightmap(lcr_sim *s, lcr_heightmap_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the map is made behind the frames, on the second stream after a step: the handle's stream waits for it here)
+    memset(out, 0, sizeof *out);
+    if (!s->height_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->height_spec;
+    for (int k = 0; k < 2; k++) out->inv_cell[k] = s->height.inv[k];
+    out->channels = s->height.channels;
+    out->slots = s->height.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->heightmap = s->height.out;
+    out->source = s->height.source;
+    out->count = s->height.count;
+    out->filled = s->height.filled;
+    out->camera_pose = s->height.pose;
+    out->bytes_per_env = (uint64_t)s->height_bytes_per_env;
     return LCR_OK;
 }
 

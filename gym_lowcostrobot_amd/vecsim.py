@@ -97,6 +97,7 @@ class VecSim:
         obs_stack=None,
         point_cloud=None,
         voxel_grid=None,
+        heightmap=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -180,6 +181,18 @@ class VecSim:
             if set(image_planes) != set(_capi.IMAGE_PLANES):
                 raise ValueError(f"voxel_grid is made of the depth and the segmentation plane: pass both, image_planes=('depth', 'segmentation') (got {image_planes!r})")
             check(self.L.lcr_voxel_grid_check(ctypes.byref(voxel_grid)))
+        # the heightmap (lcr_enable_heightmap): None = none, or a dict of box=((x0, y0, z0), (x1, y1, z1)) and dims=(Hx, Hy) -- no defaults: the caller chooses the memory --
+        # and some of cameras / ids / features ("height", "rgb") / source.  Checked here and by the library without a handle (lcr_heightmap_check), before it is asked for a
+        # device.  It is made of both planes: they are not switched on silently
+        if heightmap is not None:
+            if observation_mode == "state":
+                raise ValueError("heightmap needs image observations: observation_mode 'image' or 'both'")
+            heightmap = _capi.HeightmapSpec.from_any(heightmap)
+            if heightmap.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("heightmap: cameras selects 'wrist', but no wrist_camera is given")
+            if set(image_planes) != set(_capi.IMAGE_PLANES):
+                raise ValueError(f"heightmap is made of the depth and the segmentation plane: pass both, image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_heightmap_check(ctypes.byref(heightmap)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -379,6 +392,24 @@ class VecSim:
             self.voxel_grid_count = DeviceArray(self, vv.count, (N,), np.int32)
             self.voxel_grid_occupied = DeviceArray(self, vv.occupied, (N,), np.int32)
             self.voxel_grid_pose = DeviceArray(self, vv.camera_pose, (int(vv.slots), 13, N), np.float32)
+        # the heightmap: (N, C, Hy, Hx) float32, the input of a Conv2d as it stands
+        self.heightmap = self.heightmap_source = self.heightmap_count = self.heightmap_filled = self.heightmap_pose = self.heightmap_spec = None
+        if heightmap is not None:   # (behind look, wrist camera and planes; independent of the stack, the cloud and the grid)
+            try:
+                check(self.L.lcr_enable_heightmap(self.handle, ctypes.byref(heightmap)))
+                hv = _capi.LcrHeightmapView()
+                check(self.L.lcr_get_heightmap(self.handle, ctypes.byref(hv)))
+            except Exception:
+                self.close()
+                raise
+            # (lo, hi and inv_cell: the float32 values in use -- inv_cell is what the kernel multiplies with, the authority for which cell a point falls in)
+            self.heightmap_spec = dict(hv.spec.as_dict(), inv_cell=tuple(float(x) for x in hv.inv_cell))
+            Hx, Hy = self.heightmap_spec["dims"]
+            self.heightmap = DeviceArray(self, hv.heightmap, (N, int(hv.channels), Hy, Hx), np.float32)
+            self.heightmap_source = DeviceArray(self, hv.source, (N, Hy, Hx), np.int32) if hv.source else None
+            self.heightmap_count = DeviceArray(self, hv.count, (N,), np.int32)
+            self.heightmap_filled = DeviceArray(self, hv.filled, (N,), np.int32)
+            self.heightmap_pose = DeviceArray(self, hv.camera_pose, (int(hv.slots), 13, N), np.float32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -417,7 +448,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack, point cloud, voxel grid): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud, voxel grid, heightmap): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -653,6 +684,8 @@ class VecSim:
                 obs["point_cloud"] = self.point_cloud.numpy()
             if self.voxel_grid is not None:
                 obs["voxel_grid"] = self.voxel_grid.numpy()
+            if self.heightmap is not None:
+                obs["heightmap"] = self.heightmap.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

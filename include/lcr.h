@@ -776,6 +776,85 @@ int lcr_enable_voxel_grid(lcr_sim *sim, const lcr_voxel_grid_spec *spec);
 /* The grid; waits (on the handle's stream) for frames and grid still being made on the second stream, as every entry point but the step does. */
 int lcr_get_voxel_grid(lcr_sim *sim, lcr_voxel_grid_view *out);
 
+/* == The heightmap: an optional device buffer per handle, `heightmap` [N][C][Hy][Hx] float32, that the library keeps current behind the frame kernels -- an orthographic
+ * top-down map over a fixed axis-aligned box of the WORLD frame, fused over the cameras: channel 0 is the height of the highest surface above every cell of the table and,
+ * with LCR_HEIGHTMAP_RGB, channels 1 .. 3 its colour -- the input of Transporter-Nets / CLIPort-style "where to push, where to grasp" policies, fed straight to a Conv2d as
+ * (N, C, H, W).  It is made of ALL candidate pixels by one streaming kernel, in stream order, without a host round trip; unlike the voxel grid its height is not quantised
+ * to layers and it costs N Hx Hy elements, not N V.  Off by default: without lcr_enable_heightmap no byte, state, output or kernel of the handle changes.
+ *   inputs      those of the voxel grid: the image observations at the configured size, both planes, the selected camera slots (`cameras`: LCR_STACK_CAM_* bits, 0 = every
+ *               camera the handle has; slots in the order front, top, wrist; the wrist bit on a handle without a wrist camera is refused), `ids` (a mask over the ids 1 .. 10,
+ *               0 = 0x7FC, bit 0 and bits above 10 refused), the cameras of the handle or of the env's look variant, the wrist pose from the pose snapshot.
+ *   candidate   a pixel that is a candidate by the id rule of the point cloud (id = byte & 0x7f, bit `id` set in `ids`; the marker bit 7 is ignored).
+ *   pixel index g = slot H W + row W + px: the global pixel index, the `source` numbering of the cloud.
+ *   point       the pinned chain of "The voxel grid", word for word: hx = (float)px + 0.5f - 0.5f * (float)W;  sx = hx * s, one rounded float32 multiply;
+ *               hy = (float)row + 0.5f - 0.5f * (float)H;  sy = - (hy * s);  per axis k:  d_k = fmaf(sx, X_k, fmaf(sy, Y_k, - Z_k)),  p_k = fmaf(t, d_k, ro_k) -- with t the
+ *               float32 depth plane value and ro, X, Y, Z, s the float32 values the kernel writes to a camera_pose buffer of the map's own, [slots][13][N].  Nothing is
+ *               re-associated or contracted beyond the fmaf named, denormals are kept.
+ *   box, dims   lo[3], hi[3]: float32, FINITE, lo_k < hi_k.  dims = (Hx, Hy), each in 1 .. 256, Hx a multiple of 4, Hx Hy <= LCR_HEIGHTMAP_MAX_CELLS (16 384).  The
+ *               library forms inv_k = (float)((double)H_k / ((double)hi_k - (double)lo_k)) for k = x, y once, on the host, and REPORTS the two float32 values in the view
+ *               (inv_cell): the reported values are the authority for everything below.
+ *   cell        of a candidate, per axis k = x, y, the grid's axis rule:  u_k = p_k - lo_k, one float32 subtraction;  v_k = u_k * inv_k, one rounded float32 multiply.  The
+ *               candidate is inside along k iff u_k >= 0.0f && v_k < (float)H_k (u = - 0.0 is inside, in cell 0); then i_k = (int)v_k.  Both operations are opaque to the
+ *               optimiser.  Along x and y the box is half-open UP TO THIS ROUNDING, as the grid's is: a point a rounding below hi_k whose v_k rounds to H_k is outside.
+ *   height      u_z = p_z - lo_z, one float32 subtraction, opaque to the optimiser.  The candidate is inside along z iff u_z >= 0.0f && p_z <= hi_z: BOTH faces belong to the
+ *               box, as they belong to the crop box.  The height word hb is the bit pattern of u_z with the sign bit cleared: - 0.0 - (+ 0.0) is - 0.0, which passes the
+ *               test, and its height is + 0.0.  For u_z >= 0 the words order as the heights do.
+ *   key, map    every inside candidate has the 64-bit key ((uint64)hb << 32) | (0xFFFFFFFF - g).  A cell's value is the MAXIMUM key among its candidates: the highest
+ *               point, and among points of bit-equal height the smallest g -- front wins over top over wrist, then row-major.  An order-independent maximum: the map is
+ *               deterministic whatever the order lanes arrive in.  A cell without candidates is EMPTY, key 0; no candidate has key 0, since g < 2^32 - 1.
+ *   heightmap   [N][C][Hy][Hx] float32: x is the fastest axis; row iy is the cell row at lo_y + iy cell_y along + y of the world frame.  Channel 0: the float32 with the
+ *               bits hb, metres above lo_z; + 0.0 where empty.  With LCR_HEIGHTMAP_RGB in `features`: channels 1 .. 3, the colour-frame bytes x of the key's pixel as
+ *               (float)x * (1.0f / 255.0f), the stack's element rule, bit for bit; 0.0 where empty.
+ *   source      optional (`source` = 1), [N][Hy][Hx] int32: the g of the cell's key, - 1 where empty.
+ *   count       [N] int32, always: candidates inside the box.         filled  [N] int32, always: non-empty cells.
+ *               A cell filled at height 0.0 and an EMPTY cell hold the same bits in every channel but the colours: they differ only in `source` and `filled`.
+ *   camera_pose [slots][13][N] float32, always: ro, X, Y, Z, s of every slot per env as the kernel used them, as the cloud and the grid report them.
+ *   invariant   after every entry point that draws the batched frames -- lcr_step, lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- the map is the
+ *               function above of that env's current frames, planes and cameras.  No history and no reset rule: an auto-reset env shows its reset state, as its frames do.
+ *   ordering    the heightmap kernel runs behind the frame kernels, the stack kernel, the cloud kernel and the voxel kernel, on whatever stream they ran on; the event the
+ *               joining entry points wait for is recorded after it.  After a step on the second stream it reads the look snapshot and the pose snapshot the frames used.
+ *   life        needs image observations and BOTH planes; independent of the point cloud and the voxel grid.  Fixed for the life of the handle: the same spec again does
+ *               nothing, another spec is refused, naming both.
+ *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, the map, the same guard from the first 256-byte boundary at or behind its end (as the
+ *               grid has them), then source, count, filled and camera_pose.  Freed by lcr_destroy; LCR_ERR_OOM if it fails.
+ *   not in it   mean height and per-cell counts, oriented or per-env boxes, float16 / uint8 output, a per-cell surface id, the recorder, and the map of an episode that has
+ *               ended: there is no _terminal call, so the vector adapters refuse the map.
+ * LCR_HEIGHTMAP_ROUNDS=1|4 in the environment (read by lcr_enable_heightmap): the rounds of the scan the kernel keeps in flight, in place of the launcher's choice; the same
+ * bytes under both (an A/B switch: profiles/heightmap.txt). */
+enum { LCR_HEIGHTMAP_HEIGHT = 1, LCR_HEIGHTMAP_RGB = 2 };
+#define LCR_HEIGHTMAP_MAX_DIM 256
+#define LCR_HEIGHTMAP_MAX_CELLS 16384
+typedef struct lcr_heightmap_spec {
+    float lo[3];          /* x, y, z of the box's lower corner, world frame; finite */
+    float hi[3];          /* x, y, z of the upper corner; finite, lo[k] < hi[k] */
+    int32_t dims[2];      /* Hx, Hy: each 1 .. LCR_HEIGHTMAP_MAX_DIM, Hx a multiple of 4, Hx Hy <= LCR_HEIGHTMAP_MAX_CELLS */
+    uint32_t cameras;     /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+    uint32_t ids;         /* bit i: surface id i is a candidate, i = 1 .. 10; 0 = 0x7FC (arm and cubes) */
+    uint32_t features;    /* LCR_HEIGHTMAP_* bits; the height is implied, 0 = height only */
+    int32_t source;       /* 0 | 1: keep the source index of every cell */
+} lcr_heightmap_spec;
+typedef struct lcr_heightmap_view {
+    int32_t enabled;                   /* 0: no map, everything below is 0 / NULL */
+    lcr_heightmap_spec spec;           /* as enabled: `cameras` and `ids` resolved to the bits in use, the height bit set in `features` */
+    float inv_cell[2];                 /* inv_k: cells per metre along x, y, the float32 values the kernel multiplies with */
+    int32_t channels, slots, image_width, image_height;
+    const float *heightmap;            /* device, [N][C][Hy][Hx] */
+    const int32_t *source;             /* device, [N][Hy][Hx], or NULL */
+    const int32_t *count;              /* device, [N] */
+    const int32_t *filled;             /* device, [N] */
+    const float *camera_pose;          /* device, [slots][13][N] */
+    uint64_t bytes_per_env;            /* C Hy Hx sizeof(float) */
+} lcr_heightmap_view;
+/* The checks lcr_enable_heightmap makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field and the axis in the message -- a
+ * corner that is NaN or an infinity, lo_k >= hi_k, a dim outside 1 .. 256, Hx not a multiple of 4, more than LCR_HEIGHTMAP_MAX_CELLS cells, unknown feature bits, source
+ * other than 0 / 1, and the cloud's refusals of `cameras` and `ids` */
+int lcr_heightmap_check(const lcr_heightmap_spec *spec);
+/* Switch the map on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without both planes and a wrist bit without a wrist camera are
+ * refused (LCR_ERR_INVALID, naming what is missing); an allocation that fails is LCR_ERR_OOM.  Makes the map of the current frames. */
+int lcr_enable_heightmap(lcr_sim *sim, const lcr_heightmap_spec *spec);
+/* The map; waits (on the handle's stream) for frames and map still being made on the second stream, as every entry point but the step does. */
+int lcr_get_heightmap(lcr_sim *sim, lcr_heightmap_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */
