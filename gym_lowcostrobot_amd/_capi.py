@@ -69,6 +69,7 @@ SYMBOLS = [
     "lcr_enable_obs_stack_terminal", "lcr_get_obs_stack_terminal", "lcr_obs_stack_terminal", "lcr_point_cloud_terminal",
     "lcr_voxel_grid_check", "lcr_enable_voxel_grid", "lcr_get_voxel_grid",
     "lcr_heightmap_check", "lcr_enable_heightmap", "lcr_get_heightmap",
+    "lcr_enable_obs_stack_planes", "lcr_get_obs_stack_planes",
 ]
 
 
@@ -331,6 +332,26 @@ def take_terminal(v, what):
     if not isinstance(terminal, (bool, np.bool_)):
         raise ValueError(f"{what}: terminal must be a bool, got {terminal!r}")
     return v, bool(terminal)
+
+
+def take_stack_planes(v, image_planes):
+    """(what is left of the obs_stack argument, the LCR_PLANE_* mask of its `planes`): takes `planes` out of a dict -- a tuple or list of plane names, default (): the
+    planes the stack carries as channels beside the colours (lcr_enable_obs_stack_planes).  Only 'depth' is stacked, and only when `image_planes` has it: the plane is
+    not switched on silently"""
+    if not isinstance(v, dict) or "planes" not in v:
+        return v, 0
+    v = dict(v)
+    planes = v.pop("planes")
+    if not isinstance(planes, (tuple, list)) or not all(isinstance(p, str) for p in planes):
+        raise ValueError(f"obs_stack: planes must be a tuple or list of plane names, () or ('depth',), got {planes!r}")
+    unknown = sorted(set(planes) - set(IMAGE_PLANES))
+    if unknown:
+        raise ValueError(f"obs_stack: planes has unknown names {unknown}: () or ('depth',)")
+    if "segmentation" in planes:
+        raise ValueError("obs_stack: planes: 'segmentation' is unsupported in the stack (its ids are categorical: a cast of them is not policy-ready); () or ('depth',)")
+    if "depth" in planes and "depth" not in image_planes:
+        raise ValueError(f"obs_stack: planes=('depth',) is made of the depth plane: pass 'depth' in image_planes (got {tuple(image_planes)!r})")
+    return v, (PLANE_DEPTH if "depth" in planes else 0)
 
 
 class LcrObsStackView(ctypes.Structure):
@@ -875,6 +896,8 @@ def load():
     L.lcr_enable_obs_stack_terminal.argtypes = [vp, ctypes.POINTER(ObsStackSpec), i32]
     L.lcr_get_obs_stack_terminal.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(vp), ctypes.POINTER(u64)]
     L.lcr_obs_stack_terminal.argtypes = [vp, vp, ctypes.c_int, vp]
+    L.lcr_enable_obs_stack_planes.argtypes = [vp, ctypes.POINTER(ObsStackSpec), i32, ctypes.c_uint32]
+    L.lcr_get_obs_stack_planes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.lcr_point_cloud_terminal.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp]
     L.lcr_voxel_grid_check.argtypes = [ctypes.POINTER(VoxelGridSpec)]
     L.lcr_enable_voxel_grid.argtypes = [vp, ctypes.POINTER(VoxelGridSpec)]

@@ -41,7 +41,8 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          ("lcr_render.hip", "lcr_render_look.o", ["-DLCR_RENDER_PART=4"]),
          # the kernels of the wrist camera (lcr_enable_wrist_camera): the batched frame kernel with and without planes and looks, and its single-frame kernel
          ("lcr_render.hip", "lcr_render_wrist.o", ["-DLCR_RENDER_PART=5"]),
-         # the observation stack (lcr_enable_obs_stack): one kernel per element type and depth, a unit of its own
+         # the observation stack (lcr_enable_obs_stack): one kernel per element type and depth, each also with the depth channel (lcr_enable_obs_stack_planes), a unit of its own.
+         # The project's flags: the depth element its header pins to the bit is kept from -ffast-math inside the source (depth_unit, depth_u8)
          ("lcr_stack.hip", "lcr_stack.o", []),
          # the point cloud (lcr_enable_point_cloud): one kernel with and one without colours, a unit of its own
          ("lcr_cloud.hip", "lcr_cloud.o", []),

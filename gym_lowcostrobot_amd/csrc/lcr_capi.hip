@@ -185,6 +185,8 @@ struct lcr_sim {
     // of its own behind it; stack.history is null without it (K = 1 keeps nothing: the terminal stack is the terminal frame)
     bool stack_keep;
     size_t stack_hist_bytes_per_env;
+    // the depth channel (lcr_enable_obs_stack_planes): LCR_PLANE_DEPTH or 0; with it stack.cpc is 4, stack.depth the handle's depth planes, and depth_far is fixed
+    uint32_t stack_planes;
     // the point cloud (lcr_enable_point_cloud): one allocation -- guard, points, guard, count, source, camera poses --, fixed for the life of the handle
     bool cloud_on;
     lcr_point_cloud_spec cloud_spec;   // as enabled, cameras and ids resolved
@@ -1655,35 +1657,52 @@ int lcr_obs_stack_check(const lcr_obs_stack_spec *spec) {
 
 int lcr_enable_obs_stack(lcr_sim *s, const lcr_obs_stack_spec *spec) { return lcr_enable_obs_stack_terminal(s, spec, 0); }
 
-int lcr_enable_obs_stack_terminal(lcr_sim *s, const lcr_obs_stack_spec *spec, int32_t keep_terminal) {
+int lcr_enable_obs_stack_terminal(lcr_sim *s, const lcr_obs_stack_spec *spec, int32_t keep_terminal) { return lcr_enable_obs_stack_planes(s, spec, keep_terminal, 0); }
+
+int lcr_enable_obs_stack_planes(lcr_sim *s, const lcr_obs_stack_spec *spec, int32_t keep_terminal, uint32_t planes) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_obs_stack_check(spec)) return rc;
     if (keep_terminal != 0 && keep_terminal != 1) return fail(LCR_ERR_INVALID, "keep_terminal must be 0 or 1, got %d", keep_terminal);
+    if (planes & ~(uint32_t)(LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION))
+        return fail(LCR_ERR_INVALID, "planes must be 0 (colours only) or LCR_PLANE_DEPTH (1), got %u", planes);
+    if (planes & LCR_PLANE_SEGMENTATION)
+        return fail(LCR_ERR_UNSUPPORTED, "the segmentation plane is not stacked: its ids are categorical, and a cast of them is not policy-ready (planes %u; the depth plane, 1, is)", planes);
     SIMCHK(s);
     if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to stack");
     lcr_obs_stack_spec sp = *spec;
     if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
     if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the stack)");
     if (s->stack_on) {
+        if (s->stack_planes != planes)
+            return fail(LCR_ERR_INVALID, "an observation stack with planes %u is enabled already and fixed for the life of the handle (asked for planes %u)", s->stack_planes, planes);
         if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0 && s->stack_keep == (keep_terminal == 1)) return LCR_OK;
         if (memcmp(&s->stack_spec, &sp, sizeof sp) == 0)
             return fail(LCR_ERR_INVALID, "an observation stack with keep_terminal %d is enabled already and fixed for the life of the handle (asked for keep_terminal %d)", s->stack_keep ? 1 : 0, keep_terminal);
         return fail(LCR_ERR_INVALID, "an observation stack (frames %d, cameras %u, dtype %d, reset_fill %d) is enabled already and fixed for the life of the handle", s->stack_spec.frames,
                     s->stack_spec.cameras, s->stack_spec.dtype, s->stack_spec.reset_fill);
     }
+    // the depth channel is made of the depth plane, which is not switched on silently (the rule of the cloud, the grid and the map)
+    const bool dep = planes & LCR_PLANE_DEPTH;
+    if (dep && !(s->planes & LCR_PLANE_DEPTH))
+        return fail(LCR_ERR_INVALID, "planes asks for the depth channel, but the depth plane of this sim is not enabled (lcr_enable_image_planes with LCR_PLANE_DEPTH, before the stack)");
     LcrStack A{};
-    if (sp.cameras & LCR_STACK_CAM_FRONT) A.src[A.ncam++] = s->dev.img_front;
-    if (sp.cameras & LCR_STACK_CAM_TOP) A.src[A.ncam++] = s->dev.img_top;
-    if (sp.cameras & LCR_STACK_CAM_WRIST) A.src[A.ncam++] = s->wrist.img;
+    A.cpc = dep ? 4 : 3;
+    if (sp.cameras & LCR_STACK_CAM_FRONT) { A.depth[A.ncam] = dep ? s->pl.depth_front : nullptr; A.src[A.ncam++] = s->dev.img_front; }
+    if (sp.cameras & LCR_STACK_CAM_TOP) { A.depth[A.ncam] = dep ? s->pl.depth_top : nullptr; A.src[A.ncam++] = s->dev.img_top; }
+    if (sp.cameras & LCR_STACK_CAM_WRIST) { A.depth[A.ncam] = dep ? s->wrist.depth : nullptr; A.src[A.ncam++] = s->wrist.img; }
+    if (dep) {   // the two constants of the element rule, fixed here: depth_far cannot change once planes are on
+        A.inv_far = (float)(1.0 / (double)s->pl.far);
+        A.s255 = (float)(255.0 / (double)s->pl.far);
+    }
     const size_t N = (size_t)s->dev.n, px = (size_t)s->dev.img_h * s->dev.img_w, esize = sp.dtype == LCR_STACK_UINT8 ? 1 : sp.dtype == LCR_STACK_FLOAT16 ? 2 : 4;
-    const size_t per_env = (size_t)sp.frames * 3 * A.ncam * px * esize;
+    const size_t per_env = (size_t)sp.frames * A.cpc * A.ncam * px * esize;
     // guard, stack, guard (include/lcr.h: LCR_WRIST_GUARD), then the two snapshots of did_reset
     Carver C;
     C.skip(LCR_WRIST_GUARD);
     const size_t o_dst = C.take(N * per_env);
     C.skip(LCR_WRIST_GUARD);
     // ... with keep_terminal and older slots to keep: the history and a guard behind it (the guard before it is the stack's second)
-    const size_t hist_env = keep_terminal && sp.frames > 1 ? (size_t)(sp.frames - 1) * 3 * A.ncam * px * esize : 0;
+    const size_t hist_env = keep_terminal && sp.frames > 1 ? (size_t)(sp.frames - 1) * A.cpc * A.ncam * px * esize : 0;
     const size_t o_hist = C.take(N * hist_env);
     if (hist_env) C.skip(LCR_WRIST_GUARD);
     const size_t guarded = C.off;
@@ -1713,6 +1732,7 @@ int lcr_enable_obs_stack_terminal(lcr_sim *s, const lcr_obs_stack_spec *spec, in
     s->stack_bytes_per_env = per_env;
     s->stack_keep = keep_terminal == 1;
     s->stack_hist_bytes_per_env = hist_env;
+    s->stack_planes = planes;
     for (int p = 0; p < 2; p++) s->snap_reset[p] = s->rstream ? (unsigned char *)(base + o_snap[p]) : nullptr;
     s->stack_on = true;
     return LCR_OK;
@@ -1725,11 +1745,21 @@ int lcr_get_obs_stack(lcr_sim *s, lcr_obs_stack_view *out) {
     if (!s->stack_on) return LCR_OK;
     out->enabled = 1;
     out->spec = s->stack_spec;
-    out->channels = 3 * s->stack.ncam;
+    out->channels = s->stack.cpc * s->stack.ncam;
     out->image_width = s->dev.img_w;
     out->image_height = s->dev.img_h;
     out->data = s->stack.dst;
     out->bytes_per_env = (uint64_t)s->stack_bytes_per_env;
+    return LCR_OK;
+}
+
+int lcr_get_obs_stack_planes(lcr_sim *s, uint32_t *planes, float *inv_far, float *s255) {
+    if (!s || !planes || !inv_far || !s255) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (a joining entry point, as lcr_get_obs_stack is)
+    const bool dep = s->stack_on && (s->stack_planes & LCR_PLANE_DEPTH);
+    *planes = s->stack_on ? s->stack_planes : 0;
+    *inv_far = dep ? s->stack.inv_far : 0.f;
+    *s255 = dep ? s->stack.s255 : 0.f;
     return LCR_OK;
 }
 
@@ -1748,26 +1778,37 @@ int lcr_obs_stack_terminal(lcr_sim *s, const int32_t *env_ids_host, int count, v
     if (!s->stack_on) return fail(LCR_ERR_INVALID, "no observation stack is enabled on this sim (lcr_enable_obs_stack_terminal)");
     if (!s->stack_keep) return fail(LCR_ERR_INVALID, "the observation stack of this sim was enabled without keep_terminal: the history of an episode that ends is not kept (lcr_enable_obs_stack_terminal)");
     if (count < 0 || (count > 0 && (!env_ids_host || !out_host))) return fail(LCR_ERR_INVALID, "NULL argument");
-    const size_t img = (size_t)s->dev.img_h * s->dev.img_w * 3, env_out = s->stack_bytes_per_env;
+    const size_t px = (size_t)s->dev.img_h * s->dev.img_w, img = px * 3, env_out = s->stack_bytes_per_env;
     const bool wrist = s->stack_spec.cameras & LCR_STACK_CAM_WRIST;
-    const size_t per_env[] = {img, img, wrist ? img : 0, env_out};   // the terminal frames of front, top and -- if it is stacked -- wrist, the terminal stacks
+    // with the depth channel: the terminal depth planes too, drawn as lcr_render_terminal_planes / lcr_render_terminal_wrist draw them (0 bytes without it: no room taken)
+    const bool dep = s->stack_planes & LCR_PLANE_DEPTH;
+    const size_t dpx = dep ? px * sizeof(float) : 0;
+    // the terminal frames of front, top and -- if it is stacked -- wrist, the terminal stacks, the terminal depth planes of the three
+    const size_t per_env[] = {img, img, wrist ? img : 0, env_out, dpx, dpx, wrist ? dpx : 0};
     return render_terminal_passes(s, env_ids_host, count, per_env, [&](LcrDev &P1, const LcrLook &LK, int c, size_t done, char *const *buf) -> int {
         P1.img_front = (unsigned char *)buf[0];
         P1.img_top = (unsigned char *)buf[1];
-        if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, nullptr, s->stream));
+        if (dep) {
+            LcrPlanes PL1 = s->pl;
+            PL1.depth_front = (float *)buf[4];
+            PL1.depth_top = (float *)buf[5];
+            PL1.seg_front = nullptr; PL1.seg_top = nullptr;
+            if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, &PL1, s->stream));
+            else LAUNCHCHK("render", lcr_launch_render_obs_planes(P1, s->cam_front, s->cam_top, PL1, s->stream));
+        } else if (s->look_K) LAUNCHCHK("render", lcr_launch_render_obs_look(P1, LK, nullptr, s->stream));
         else LAUNCHCHK("render", lcr_launch_render_obs(P1, s->cam_front, s->cam_top, s->stream));
         if (wrist) {
             LcrWrist W1 = s->wrist;
             W1.img = (unsigned char *)buf[2];
-            W1.depth = nullptr; W1.seg = nullptr;
+            W1.depth = (float *)buf[6]; W1.seg = nullptr;   // (buf[6] is null without the depth channel)
             LAUNCHCHK("render", lcr_launch_render_wrist(P1, W1, s->look_K ? &LK : nullptr, s->stream));
         }
         // slots 0 .. K - 2 from the history of the listed envs, slot K - 1 the terminal frames by the stack's transpose and cast
         LcrStack A = s->stack;
         A.ncam = 0;
-        if (s->stack_spec.cameras & LCR_STACK_CAM_FRONT) A.src[A.ncam++] = (const unsigned char *)buf[0];
-        if (s->stack_spec.cameras & LCR_STACK_CAM_TOP) A.src[A.ncam++] = (const unsigned char *)buf[1];
-        if (wrist) A.src[A.ncam++] = (const unsigned char *)buf[2];
+        if (s->stack_spec.cameras & LCR_STACK_CAM_FRONT) { A.depth[A.ncam] = (const float *)buf[4]; A.src[A.ncam++] = (const unsigned char *)buf[0]; }
+        if (s->stack_spec.cameras & LCR_STACK_CAM_TOP) { A.depth[A.ncam] = (const float *)buf[5]; A.src[A.ncam++] = (const unsigned char *)buf[1]; }
+        if (wrist) { A.depth[A.ncam] = (const float *)buf[6]; A.src[A.ncam++] = (const unsigned char *)buf[2]; }
         A.dst = buf[3];
         A.n = c;
         A.flags = nullptr; A.op = LCR_STACK_NEWEST;

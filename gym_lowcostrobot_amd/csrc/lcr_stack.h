@@ -18,7 +18,7 @@ enum { LCR_STACK_MODE_PLAIN = 0, LCR_STACK_MODE_SAVE = 1, LCR_STACK_MODE_TERMINA
 
 struct LcrStack {
     const unsigned char *src[3];   // the selected cameras' frames in channel order, [n][pixels][3] each; src[i >= ncam] unused
-    void *dst;                     // [n][frames][3 ncam][pixels] of the element type
+    void *dst;                     // [n][frames][cpc ncam][pixels] of the element type
     const unsigned char *flags;    // [n] or null
     int n, ncam, pixels;           // pixels = img_h * img_w, a multiple of 16
     int frames;                    // K, 1 .. 8
@@ -28,6 +28,11 @@ struct LcrStack {
     int mode;                      // LCR_STACK_MODE_*
     void *history;                 // [N][frames - 1][3 ncam][pixels] of the element type (SAVE: written, TERMINAL: read), or null
     const int *ids;                // TERMINAL: [n] env ids of the view's envs, the rows of `history`
+    // the depth channel (lcr_enable_obs_stack_planes with the depth bit): cpc = 4 channel planes per camera, r g b d -- dst and history are then [..][4 ncam][pixels] --,
+    // 3 without it (nothing below is looked at, and the kernel that runs is the colour stack's)
+    int cpc;
+    const float *depth[3];         // the selected cameras' depth planes in channel order, [n][pixels] float32 each
+    float inv_far, s255;           // (float)(1.0 / (double)depth_far), (float)(255.0 / (double)depth_far): the constants of the element rule (include/lcr.h)
 };
 
 // 0, or the hipError_t of the launch; -1: arguments the kernel is not built for (nothing is launched)

@@ -58,7 +58,8 @@ def _obs_spaces(sim, observation_mode):
         for k in sim.plane_arrays():   # VecSim(image_planes=...): depth_front / depth_top in metres up to depth_far, segmentation_front / segmentation_top ids (include/lcr.h)
             subs[k] = sp.Box(0.0, sim.depth_far, shape=sim.image_size, dtype=np.float32) if k.startswith("depth_") else sp.Box(0, 255, shape=sim.image_size, dtype=np.uint8)
         # VecSim(obs_stack=dict(..., terminal=True)) / (point_cloud=dict(..., terminal=True)): the stack (K, C, H, W) of its element type and the cloud (P, C), for which
-        # the library can make the terminal observation as well.  Without terminal=True neither is exposed (count, source and pose of the cloud are no observations)
+        # the library can make the terminal observation as well.  Without terminal=True neither is exposed (count, source and pose of the cloud are no observations).
+        # With planes=("depth",) the stack is RGB-D, C = 4 per camera: the depth channel lies in [0, 1] (0 .. 255 as uint8) as the colours do, so the bounds hold
         if sim.obs_stack is not None and sim.obs_stack_keeps_terminal:
             dt = sim.obs_stack.dtype
             subs["obs_stack"] = sp.Box(0, 255, shape=sim.obs_stack.shape[1:], dtype=np.uint8) if dt == np.uint8 else sp.Box(0.0, 1.0, shape=sim.obs_stack.shape[1:], dtype=dt.type)

@@ -138,11 +138,14 @@ class VecSim:
         # the observation stack (lcr_enable_obs_stack): None = none, an int = that many frames of every camera as uint8, or a dict of frames / cameras / dtype / reset_fill.
         # Checked here and by the library without a handle (lcr_obs_stack_check), before it is asked for a device
         # terminal=True in the dict (lcr_enable_obs_stack_terminal): the library keeps the history of an episode that ends, obs_stack_terminal() returns its stack
+        # planes=("depth",) in the dict (lcr_enable_obs_stack_planes): every camera contributes r, g, b, d -- the depth plane, which image_planes must have, as a channel
         stack_terminal = cloud_terminal = False
+        stack_planes = 0
         if obs_stack is not None:
             if observation_mode == "state":
                 raise ValueError("obs_stack needs image observations: observation_mode 'image' or 'both'")
             obs_stack, stack_terminal = _capi.take_terminal(obs_stack, "obs_stack")
+            obs_stack, stack_planes = _capi.take_stack_planes(obs_stack, image_planes)
             obs_stack = _capi.ObsStackSpec.from_any(obs_stack)
             if obs_stack.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
                 raise ValueError("obs_stack: cameras selects 'wrist', but no wrist_camera is given")
@@ -333,18 +336,26 @@ class VecSim:
         self.obs_stack = self.obs_stack_spec = None
         self.obs_stack_keeps_terminal = False   # obs_stack=dict(..., terminal=True): obs_stack_terminal() works
         self.obs_stack_history = None           # ... and, with more than one frame, the history (N, K - 1, C, H, W) the library keeps for it
+        self.obs_stack_planes = ()              # obs_stack=dict(..., planes=("depth",)): ("depth",), every camera's channels are r, g, b, d
+        self.obs_stack_depth_scale = None       # ... and {"inv_far": ..., "s255": ...}, the float32 constants of the depth element as the library holds them
         self.point_cloud_wants_terminal = cloud_terminal   # point_cloud=dict(..., terminal=True): what the vector adapters look at; point_cloud_terminal() works either way
         if obs_stack is not None:   # (last: behind look, wrist camera and planes)
             try:
-                check(self.L.lcr_enable_obs_stack_terminal(self.handle, ctypes.byref(obs_stack), int(stack_terminal)))   # (terminal False: lcr_enable_obs_stack)
+                # (planes 0: lcr_enable_obs_stack_terminal; terminal False too: lcr_enable_obs_stack)
+                check(self.L.lcr_enable_obs_stack_planes(self.handle, ctypes.byref(obs_stack), int(stack_terminal), int(stack_planes)))
                 sv = _capi.LcrObsStackView()
                 check(self.L.lcr_get_obs_stack(self.handle, ctypes.byref(sv)))
+                pmask, inv_far, s255 = ctypes.c_uint32(0), ctypes.c_float(0), ctypes.c_float(0)
+                check(self.L.lcr_get_obs_stack_planes(self.handle, ctypes.byref(pmask), ctypes.byref(inv_far), ctypes.byref(s255)))
                 keep, hist, hist_bytes = ctypes.c_int32(0), ctypes.c_void_p(), ctypes.c_uint64(0)
                 check(self.L.lcr_get_obs_stack_terminal(self.handle, ctypes.byref(keep), ctypes.byref(hist), ctypes.byref(hist_bytes)))
             except Exception:
                 self.close()
                 raise
             self.obs_stack_keeps_terminal = bool(keep.value)
+            if pmask.value & _capi.PLANE_DEPTH:
+                self.obs_stack_planes = ("depth",)
+                self.obs_stack_depth_scale = {"inv_far": float(inv_far.value), "s255": float(s255.value)}
             if hist.value:
                 self.obs_stack_history = DeviceArray(self, hist.value, (N, int(sv.spec.frames) - 1, int(sv.channels)) + self.image_size, np.dtype(sv.spec.as_dict()["dtype"]))
             self.obs_stack_spec = sv.spec.as_dict()

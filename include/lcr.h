@@ -496,7 +496,8 @@ int lcr_render_terminal_wrist(lcr_sim *sim, const int32_t *env_ids_host, int cou
  *             (N bytes beside the pose snapshots, two in turn): without it the step kernel of step k + 1 would overwrite the flags the stack of step k still has to read.
  *             The event every other entry point waits for is recorded after the stack kernel: every entry point but the step sees a finished stack.
  *   life      enabled last -- after look, wrist camera and planes -- and fixed for the life of the handle: the same arguments again do nothing, other arguments are refused,
- *             and lcr_enable_look / lcr_enable_wrist_camera on a handle whose stack is on are refused.  The planes are not stacked; they may be enabled before or after.
+ *             and lcr_enable_look / lcr_enable_wrist_camera on a handle whose stack is on are refused.  The planes are not stacked unless asked for ("The depth channel" below:
+ *             lcr_enable_obs_stack_planes); without the depth channel they may be enabled before or after.
  *   guards    the stack lies between two regions of LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, [data - LCR_WRIST_GUARD, data) and LCR_WRIST_GUARD bytes from the first
  *             256-byte boundary at or behind its end; filled once, never written afterwards.
  *   not kept  unless asked for, the stack of an episode that ended: the refill overwrites the K - 1 older frames of a reset env.  "Terminal observation stacks" below keeps
@@ -541,7 +542,8 @@ int lcr_get_obs_stack(lcr_sim *sim, lcr_obs_stack_view *out);
  *   guards      the history lies behind the stack's second guard region, and LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE follow the first 256-byte boundary at or behind its
  *               end; filled once, never written afterwards.
  *   life        as the spec: the same spec and the same keep_terminal again do nothing, anything else is refused.
- *   not kept    terminal history of the depth and segmentation planes; device-side outputs of the terminal calls. */
+ *   not kept    terminal history of the depth and segmentation planes (but for the depth channel of a stack enabled with it, below); device-side outputs of the terminal
+ *               calls. */
 /* lcr_enable_obs_stack with the choice to keep terminal stacks; lcr_enable_obs_stack(sim, spec) is this call with keep_terminal = 0.  `spec` is checked first, then
  * keep_terminal (0 or 1: LCR_ERR_INVALID naming it), then the handle. */
 int lcr_enable_obs_stack_terminal(lcr_sim *sim, const lcr_obs_stack_spec *spec, int32_t keep_terminal);
@@ -554,6 +556,33 @@ int lcr_get_obs_stack_terminal(lcr_sim *sim, int32_t *keep_terminal, const void 
  * frames are drawn and the stacks assembled in device staging, in as many passes as keep the staging -- per env the terminal frames of front, top and (if stacked) wrist and the
  * terminal stack -- within the 450 MiB a pass of the terminal-frame calls takes. */
 int lcr_obs_stack_terminal(lcr_sim *sim, const int32_t *env_ids_host, int count, void *out_host);
+
+/* == The depth channel of the observation stack: RGB-D for a convolutional policy.  Off unless asked for: a handle enabled with lcr_enable_obs_stack or
+ * lcr_enable_obs_stack_terminal, or with planes = 0, launches the stack kernel it always launched and produces its bytes.
+ *   channels    a stack enabled with the depth plane has C = 4 x (number of selected cameras) channels.  The cameras keep the order front, top, wrist; each contributes
+ *               r, g, b, d.
+ *   the same    slots, push, refill (repeat / zero), lcr_reset, lcr_set_look, enabling, ordering on the second stream, guards and life are word for word those of the colour
+ *               stack: the depth channel is one more channel that moves with the others.  A zero refill writes zero bits to the depth channel too.  The colour channels of a
+ *               depth stack follow the existing rule unchanged.
+ *   elements    d is the float32 of the depth plane: metres along the optical axis, already clipped to [0, depth_far] by the frame kernel.  Two float32 constants are fixed
+ *               when the stack is enabled, inv_far = (float)(1.0 / (double)depth_far) and s255 = (float)(255.0 / (double)depth_far).
+ *               LCR_STACK_FLOAT32: fminf(d * inv_far, 1.0f) -- ONE rounded float32 multiply, then the clamp.  LCR_STACK_FLOAT16: that float32 value rounded to nearest even.
+ *               LCR_STACK_UINT8: min((int)fmaf(d, s255, 0.5f), 255) -- ONE fused multiply-add, truncation toward zero, then the clamp.  Nothing in these chains is
+ *               re-associated or contracted differently by the build's fast-math flags: they are pinned as the crop box's point chain is.
+ *   enabling    the depth channel is made of the depth plane, which is not switched on silently: with the depth bit the planes must be enabled BEFORE the stack, and a handle
+ *               whose depth plane is not enabled is refused by name.  depth_far is then fixed: a later lcr_enable_image_planes with another depth_far is refused.
+ *   terminal    with keep_terminal = 1 the history is [N][K - 1][4 ncam][H][W] and carries the depth channel; lcr_obs_stack_terminal returns [count][K][4 ncam][H][W], its
+ *               staging additionally holds the terminal depth planes of the selected cameras, drawn the way lcr_render_terminal_planes / lcr_render_terminal_wrist draw
+ *               them: same poses, same terminal looks.
+ *   not in it   a segmentation channel (ids are categorical: a cast of them is not policy-ready); normalisation by mean and std; a depth-only stack without colours;
+ *               per-camera depth_far; the recorder. */
+/* lcr_enable_obs_stack_terminal with the choice of planes: `planes` is a mask of the LCR_PLANE_* bits lcr_enable_image_planes uses.  planes = 0 is exactly
+ * lcr_enable_obs_stack_terminal; LCR_PLANE_DEPTH asks for the RGB-D stack; LCR_PLANE_SEGMENTATION is LCR_ERR_UNSUPPORTED, named in the message; unknown bits are
+ * LCR_ERR_INVALID.  `spec` is checked first, then keep_terminal, then planes, then the handle: a handle whose depth plane is not enabled is refused by name (LCR_ERR_INVALID),
+ * and so is a stack enabled already with another mask. */
+int lcr_enable_obs_stack_planes(lcr_sim *sim, const lcr_obs_stack_spec *spec, int32_t keep_terminal, uint32_t planes);
+/* The mask in use and the two constants of the depth element as the float32 values in use; 0, 0, 0 without a depth channel.  Joins as lcr_get_obs_stack does. */
+int lcr_get_obs_stack_planes(lcr_sim *sim, uint32_t *planes, float *inv_far, float *s255);
 
 /* == The point cloud: an optional device buffer per handle, `points` [N][P][C] float32, that the library keeps current behind the frame kernels -- a fixed number of
  * world-frame points per env, fused over the cameras, floor and sky dropped: the input of a PointNet-style encoder or a 3-D diffusion policy.  Everything it is made of
