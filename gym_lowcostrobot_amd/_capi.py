@@ -48,6 +48,12 @@ VOXEL_MAX_DIM, VOXEL_MAX_CELLS = 64, 32768
 # the heightmap (lcr_enable_heightmap): LCR_HEIGHTMAP_* feature bits, LCR_HEIGHTMAP_MAX_DIM, LCR_HEIGHTMAP_MAX_CELLS; its cameras and ids are the cloud's
 HEIGHTMAP_FEATURES = {"height": 1, "rgb": 2}
 HEIGHTMAP_MAX_DIM, HEIGHTMAP_MAX_CELLS = 256, 16384
+# the object boxes (lcr_enable_object_boxes): LCR_BOXES_MAX_OBJECTS, LCR_BOXES_MARKER, the names of an object's parts as masks over the surface ids, the eight fields of a record
+BOXES_MAX_OBJECTS, BOXES_MARKER = 16, 0x80000000
+BOXES_OBJECTS = {"floor": 1 << 1, "arm": 0x7F << 2, "cube": 1 << 9, "cube2": 1 << 10, "marker": BOXES_MARKER, "base_link": 1 << 2,
+                 **{f"link_{i}": 1 << (2 + i) for i in range(1, 7)}}
+BOXES_DEFAULT_OBJECTS = ("arm", "cube", "cube2", "marker")   # the same for every task: an object a task does not have gives empty records, the shape does not depend on the task
+BOXES_FIELDS = ("x0", "y0", "x1", "y1", "count", "sum_x", "sum_y", "nearest")
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -69,6 +75,7 @@ SYMBOLS = [
     "lcr_enable_obs_stack_terminal", "lcr_get_obs_stack_terminal", "lcr_obs_stack_terminal", "lcr_point_cloud_terminal",
     "lcr_voxel_grid_check", "lcr_enable_voxel_grid", "lcr_get_voxel_grid",
     "lcr_heightmap_check", "lcr_enable_heightmap", "lcr_get_heightmap",
+    "lcr_object_boxes_check", "lcr_enable_object_boxes", "lcr_get_object_boxes",
     "lcr_enable_obs_stack_planes", "lcr_get_obs_stack_planes",
 ]
 
@@ -759,6 +766,95 @@ class LcrHeightmapView(ctypes.Structure):
     ]
 
 
+class ObjectBoxesSpec(ctypes.Structure):
+    """lcr_object_boxes_spec: cameras, objects (masks over the surface ids and the marker) and the depth switch of the object boxes (include/lcr.h)"""
+    _fields_ = [
+        ("cameras", ctypes.c_uint32),                      # STACK_CAMERAS bits, at least one
+        ("n_objects", ctypes.c_int32),                     # 1 .. BOXES_MAX_OBJECTS
+        ("objects", ctypes.c_uint32 * BOXES_MAX_OBJECTS),  # [i < n_objects]: bits 1 .. 10 and BOXES_MARKER
+        ("depth", ctypes.c_int32),                         # 0 | 1: keep the nearest depth word of every record
+    ]
+    given = None   # the objects as the caller named them (from_any)
+
+    def as_dict(self):
+        """cameras as names, the objects as given (the masks where a raw spec gave none), the masks, depth as a bool"""
+        masks = tuple(int(self.objects[i]) for i in range(self.n_objects))
+        return {"cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b), "objects": masks if self.given is None else self.given, "masks": masks,
+                "depth": bool(self.depth)}
+
+    @staticmethod
+    def mask_of(obj):
+        """the mask of one object: a name of BOXES_OBJECTS, a surface id 1 .. 10, or a tuple of those (their union); None if it is none of these"""
+        import numpy as np
+
+        if isinstance(obj, str):
+            return BOXES_OBJECTS.get(obj)
+        if isinstance(obj, (int, np.integer)) and not isinstance(obj, (bool, np.bool_)):
+            return 1 << int(obj) if 1 <= obj <= 10 else None
+        if isinstance(obj, (tuple, list)) and len(obj) > 0:
+            parts = [None if isinstance(o, (tuple, list)) else ObjectBoxesSpec.mask_of(o) for o in obj]
+            if None not in parts:
+                m = 0
+                for x in parts:
+                    m |= x
+                return m
+        return None
+
+    @classmethod
+    def from_any(cls, v, wrist=False):
+        """an ObjectBoxesSpec, True (the defaults), or a dict with some of objects / cameras / depth.  `wrist`: the handle has a wrist camera (the default cameras are every
+        camera the handle has)"""
+        import numpy as np
+
+        if isinstance(v, cls):
+            return v
+        if v is True:
+            v = {}
+        if not isinstance(v, dict):
+            raise ValueError(f"object_boxes must be None, True or a dict of objects / cameras / depth, got {v!r}")
+        v = dict(v)
+        out = cls()
+        names = "'" + "', '".join(BOXES_OBJECTS) + "'"
+        objects = v.pop("objects", BOXES_DEFAULT_OBJECTS)
+        what = (f"object_boxes: objects must be a non-empty tuple of at most {BOXES_MAX_OBJECTS} objects, each a name drawn from {names}, a surface id 1 .. 10 "
+                f"or a tuple of those (their union)")
+        if isinstance(objects, str) or not isinstance(objects, (tuple, list)) or not 1 <= len(objects) <= BOXES_MAX_OBJECTS:
+            raise ValueError(f"{what}, got {objects!r}")
+        for i, obj in enumerate(objects):
+            m = cls.mask_of(obj)
+            if m is None:
+                raise ValueError(f"{what}; objects[{i}] is {obj!r}")
+            out.objects[i] = m
+        out.n_objects = len(objects)
+        out.given = tuple(tuple(o) if isinstance(o, list) else o for o in objects)
+        cams = v.pop("cameras", None)
+        if cams is None:
+            out.cameras = STACK_CAMERAS["front"] | STACK_CAMERAS["top"] | (STACK_CAMERAS["wrist"] if wrist else 0)
+        else:
+            if isinstance(cams, str) or not hasattr(cams, "__iter__") or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"object_boxes: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        depth = v.pop("depth", False)
+        if not isinstance(depth, (bool, np.bool_)):
+            raise ValueError(f"object_boxes: depth must be a bool, got {depth!r}")
+        out.depth = int(depth)
+        if v:
+            raise ValueError(f"unknown object_boxes fields {sorted(v)}")
+        return out
+
+
+class LcrObjectBoxesView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", ObjectBoxesSpec),           # as enabled; the masks beyond n_objects are 0
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("boxes", ctypes.c_void_p),          # [N][slots][O][8] int32
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -905,6 +1001,9 @@ def load():
     L.lcr_heightmap_check.argtypes = [ctypes.POINTER(HeightmapSpec)]
     L.lcr_enable_heightmap.argtypes = [vp, ctypes.POINTER(HeightmapSpec)]
     L.lcr_get_heightmap.argtypes = [vp, ctypes.POINTER(LcrHeightmapView)]
+    L.lcr_object_boxes_check.argtypes = [ctypes.POINTER(ObjectBoxesSpec)]
+    L.lcr_enable_object_boxes.argtypes = [vp, ctypes.POINTER(ObjectBoxesSpec)]
+    L.lcr_get_object_boxes.argtypes = [vp, ctypes.POINTER(LcrObjectBoxesView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

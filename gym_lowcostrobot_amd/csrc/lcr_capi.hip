@@ -17,6 +17,7 @@
 #include "lcr_cloud.h"
 #include "lcr_voxel.h"
 #include "lcr_heightmap.h"
+#include "lcr_boxes.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -207,6 +208,11 @@ struct lcr_sim {
     LcrHeightmap height;               // the arguments of its kernel (the cameras and the pose snapshot are set per launch)
     void *height_mem;
     size_t height_bytes_per_env;
+    // the object boxes (lcr_enable_object_boxes): one allocation -- guard, records, guard --, fixed for the life of the handle
+    bool boxes_on;
+    lcr_object_boxes_spec boxes_spec;  // as enabled, the masks beyond n_objects zero
+    LcrBoxes boxes;                    // the arguments of their kernel: a view of the handle's own planes
+    void *boxes_mem;
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -282,13 +288,15 @@ static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, con
 }
 
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
-// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, and on one with a heightmap its kernel last
+// handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, on
+// one with a heightmap its kernel, and on one with object boxes their kernel last (it reads the planes alone: no camera, no look, no pose)
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
     if (s->cloud_on) LAUNCHCHK("point-cloud kernel", launch_cloud(s, P, stream, look));
     if (s->voxel_on) LAUNCHCHK("voxel-grid kernel", launch_voxel(s, P, stream, look));
     if (s->height_on) LAUNCHCHK("heightmap kernel", launch_heightmap(s, P, stream, look));
+    if (s->boxes_on) LAUNCHCHK("object-boxes kernel", lcr_launch_object_boxes(s->boxes, stream));
     return LCR_OK;
 }
 
@@ -792,6 +800,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->cloud_mem) (void)hipFree(s->cloud_mem);
     if (s->voxel_mem) (void)hipFree(s->voxel_mem);
     if (s->height_mem) (void)hipFree(s->height_mem);
+    if (s->boxes_mem) (void)hipFree(s->boxes_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -2321,6 +2330,95 @@ int lcr_get_heightmap(lcr_sim *s, lcr_heightmap_view *out) {
     out->filled = s->height.filled;
     out->camera_pose = s->height.pose;
     out->bytes_per_env = (uint64_t)s->height_bytes_per_env;
+    return LCR_OK;
+}
+
+// ---- the object boxes ----
+
+int lcr_object_boxes_check(const lcr_object_boxes_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (spec->cameras == 0 || (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST)))
+        return fail(LCR_ERR_INVALID, "cameras must be a non-empty mask of 1 (front), 2 (top) and 4 (wrist), got %u", spec->cameras);
+    if (spec->n_objects < 1 || spec->n_objects > LCR_BOXES_MAX_OBJECTS) return fail(LCR_ERR_INVALID, "n_objects must be in 1 .. %d, got %d", LCR_BOXES_MAX_OBJECTS, spec->n_objects);
+    for (int o = 0; o < spec->n_objects; o++) {
+        const uint32_t m = spec->objects[o];
+        if (m == 0) return fail(LCR_ERR_INVALID, "objects[%d] is empty: an object is a mask over the surface ids 1 .. 10 (bits 1 .. 10) and the marker (0x80000000)", o);
+        if (m & 1u) return fail(LCR_ERR_INVALID, "objects[%d] selects bit 0, the sky, which is no object (got 0x%x)", o, m);
+        if (m & ~(uint32_t)(0x7FEu | LCR_BOXES_MARKER))
+            return fail(LCR_ERR_INVALID, "objects[%d] selects bits 11 .. 30, which are no surface ids: a mask over bits 1 .. 10 and the marker (0x80000000), got 0x%x", o, m);
+    }
+    if (spec->depth != 0 && spec->depth != 1) return fail(LCR_ERR_INVALID, "depth must be 0 or 1, got %d", spec->depth);
+    return LCR_OK;
+}
+
+// "cameras, n objects (masks), depth" into buf: how the refusal names a spec
+static const char *boxes_spec_text(char (&buf)[320], const lcr_object_boxes_spec &v) {
+    int at = snprintf(buf, sizeof buf, "cameras %u, %d objects (", v.cameras, v.n_objects);
+    for (int o = 0; o < v.n_objects && at < (int)sizeof buf; o++) at += snprintf(buf + at, sizeof buf - at, o ? " 0x%x" : "0x%x", v.objects[o]);
+    if (at < (int)sizeof buf) snprintf(buf + at, sizeof buf - at, "), depth %d", v.depth);
+    return buf;
+}
+
+int lcr_enable_object_boxes(lcr_sim *s, const lcr_object_boxes_spec *spec) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_object_boxes_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to find objects in");
+    if (!(s->planes & LCR_PLANE_SEGMENTATION))
+        return fail(LCR_ERR_INVALID, "the object boxes are made of the segmentation plane (lcr_enable_image_planes with the segmentation bit, before the boxes): the segmentation plane is missing");
+    if (spec->depth && !(s->planes & LCR_PLANE_DEPTH))
+        return fail(LCR_ERR_INVALID, "depth = 1 keeps the nearest depth of every record, but the depth plane is missing (lcr_enable_image_planes with planes = 3, before the boxes)");
+    if ((spec->cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the boxes)");
+    lcr_object_boxes_spec sp{};
+    sp.cameras = spec->cameras; sp.n_objects = spec->n_objects; sp.depth = spec->depth;
+    for (int o = 0; o < sp.n_objects; o++) sp.objects[o] = spec->objects[o];
+    if (s->boxes_on) {
+        if (memcmp(&sp, &s->boxes_spec, sizeof sp) == 0) return LCR_OK;
+        char was[320], asked[320];
+        return fail(LCR_ERR_INVALID, "object boxes (%s) are enabled already and fixed for the life of the handle: asked for %s", boxes_spec_text(was, s->boxes_spec), boxes_spec_text(asked, sp));
+    }
+    LcrBoxes A{};
+    auto slot = [&A, &sp](const unsigned char *seg, const float *depth) { A.seg[A.slots] = seg; A.depth[A.slots] = sp.depth ? (const unsigned *)depth : nullptr; A.slots++; };
+    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(s->pl.seg_front, s->pl.depth_front);
+    if (sp.cameras & LCR_STACK_CAM_TOP) slot(s->pl.seg_top, s->pl.depth_top);
+    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(s->wrist.seg, s->wrist.depth);
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.n_objects = sp.n_objects;
+    for (int o = 0; o < sp.n_objects; o++) A.masks[o] = sp.objects[o];
+    // guard, records, guard (include/lcr.h: LCR_WRIST_GUARD)
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    const size_t o_out = C.take((size_t)A.n * A.slots * sp.n_objects * 8 * sizeof(int32_t));
+    C.skip(LCR_WRIST_GUARD);
+    const size_t off = C.off;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the object boxes failed: %s", off, hipGetErrorString(e));
+    A.out = (int *)((char *)mem + o_out);
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, off, s->stream);
+    if (!rc) rc = lcr_launch_object_boxes(A, s->stream);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); return fail(LCR_ERR_UNSUPPORTED, "the object-boxes kernel is not built for %d cameras at %d x %d with %d objects", A.slots, A.W, A.H, A.n_objects); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "making the object boxes failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->boxes = A;
+    s->boxes_mem = mem;
+    s->boxes_spec = sp;
+    s->boxes_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_object_boxes(lcr_sim *s, lcr_object_boxes_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the records are made behind the frames, on the second stream after a step: the handle's stream waits for them here)
+    memset(out, 0, sizeof *out);
+    if (!s->boxes_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->boxes_spec;
+    out->slots = s->boxes.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    out->boxes = s->boxes.out;
+    out->bytes_per_env = (uint64_t)s->boxes.slots * s->boxes.n_objects * 8 * sizeof(int32_t);
     return LCR_OK;
 }
 

@@ -98,6 +98,7 @@ class VecSim:
         point_cloud=None,
         voxel_grid=None,
         heightmap=None,
+        object_boxes=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -196,6 +197,22 @@ class VecSim:
             if set(image_planes) != set(_capi.IMAGE_PLANES):
                 raise ValueError(f"heightmap is made of the depth and the segmentation plane: pass both, image_planes=('depth', 'segmentation') (got {image_planes!r})")
             check(self.L.lcr_heightmap_check(ctypes.byref(heightmap)))
+        # the object boxes (lcr_enable_object_boxes): None / False = none, True = the defaults, or a dict with some of objects (names, surface ids, tuples of those) /
+        # cameras / depth.  Checked here and by the library without a handle (lcr_object_boxes_check), before it is asked for a device.  They are made of the segmentation
+        # plane and, with depth=True, the depth plane: neither is switched on silently
+        if object_boxes is None or object_boxes is False:
+            object_boxes = None
+        else:
+            if observation_mode == "state":
+                raise ValueError("object_boxes needs image observations: observation_mode 'image' or 'both'")
+            object_boxes = _capi.ObjectBoxesSpec.from_any(object_boxes, wrist=wrist_camera is not None)
+            if object_boxes.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("object_boxes: cameras selects 'wrist', but no wrist_camera is given")
+            if "segmentation" not in image_planes:
+                raise ValueError(f"object_boxes is made of the segmentation plane: pass it, image_planes=('segmentation',) (got {image_planes!r})")
+            if object_boxes.depth and "depth" not in image_planes:
+                raise ValueError(f"object_boxes: depth=True keeps the nearest depth of every record and needs the depth plane: image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_object_boxes_check(ctypes.byref(object_boxes)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -421,6 +438,18 @@ class VecSim:
             self.heightmap_count = DeviceArray(self, hv.count, (N,), np.int32)
             self.heightmap_filled = DeviceArray(self, hv.filled, (N,), np.int32)
             self.heightmap_pose = DeviceArray(self, hv.camera_pose, (int(hv.slots), 13, N), np.float32)
+        # the object boxes: (N, S, O, 8) int32, a record of _capi.BOXES_FIELDS per env, camera slot and object
+        self.object_boxes = self.object_boxes_spec = None
+        if object_boxes is not None:   # (behind look, wrist camera and planes; independent of the stack, the cloud, the grid and the map)
+            try:
+                check(self.L.lcr_enable_object_boxes(self.handle, ctypes.byref(object_boxes)))
+                bv = _capi.LcrObjectBoxesView()
+                check(self.L.lcr_get_object_boxes(self.handle, ctypes.byref(bv)))
+            except Exception:
+                self.close()
+                raise
+            self.object_boxes_spec = object_boxes.as_dict()
+            self.object_boxes = DeviceArray(self, bv.boxes, (N, int(bv.slots), int(bv.spec.n_objects), 8), np.int32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -459,7 +488,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack, point cloud, voxel grid, heightmap): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud, voxel grid, heightmap, object boxes): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -697,6 +726,8 @@ class VecSim:
                 obs["voxel_grid"] = self.voxel_grid.numpy()
             if self.heightmap is not None:
                 obs["heightmap"] = self.heightmap.numpy()
+            if self.object_boxes is not None:
+                obs["object_boxes"] = self.object_boxes.numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

@@ -884,6 +884,64 @@ int lcr_enable_heightmap(lcr_sim *sim, const lcr_heightmap_spec *spec);
 /* The map; waits (on the handle's stream) for frames and map still being made on the second stream, as every entry point but the step does. */
 int lcr_get_heightmap(lcr_sim *sim, lcr_heightmap_view *out);
 
+/* == Object boxes: an optional device buffer per handle, `boxes` [N][slots][O][8] int32, that the library keeps current behind the frame kernels -- per env, camera and
+ * object the tight 2-D box of the object's VISIBLE pixels, their count, their coordinate sums and the nearest depth among them: where an object is in a frame, how much of
+ * it shows, whether it shows at all.  The labels of object-centric and keypoint policies, of visibility and occlusion terms ("is the cube in the wrist camera"), of attention
+ * crops and of auto-labelled detection sets under visual domain randomisation.  One streaming kernel reads every segmentation byte once and makes every object's record, in
+ * stream order, without a host round trip.  Off by default: without lcr_enable_object_boxes no byte, state, output or kernel of the handle changes.
+ *   inputs      the segmentation planes of the selected camera slots at the configured size [H][W] (`cameras`: LCR_STACK_CAM_* bits, at least one; slots in the order front,
+ *               top, wrist, as the cloud has them; the wrist bit on a handle without a wrist camera is refused) and, with `depth` = 1, their depth planes.
+ *   object      a 32-bit mask m.  Bits 1 .. 10 select surface ids of the segmentation plane (1 the floor, 2 .. 8 base_link and link_1 .. link_6, 9 the cube, 10 the second
+ *               cube); LCR_BOXES_MARKER (0x80000000u) selects the target marker, bit 7 of the byte.  Bit 0 (the sky, which is no object), bits 11 .. 30 and an empty mask are
+ *               refused.  Objects may overlap: "arm" (0x1FC) beside "link_6" (0x100), "cube" beside the union of both cubes (0x600).  1 .. LCR_BOXES_MAX_OBJECTS objects.
+ *   match       a segmentation byte b matches object m iff ((m >> (b & 0x7f)) & 1) != 0, or (m & LCR_BOXES_MARKER) && (b & 0x80).  (The planes hold the ids 0 .. 10; an id
+ *               of 31 or more, which no plane holds, selects no bit.)  A cube pixel under the marker matches the cube AND the marker.
+ *   record      eight int32 over the matching pixels (r, c) of the plane, r the row and c the column:
+ *                 0 x0 = min c     1 y0 = min r     2 x1 = max c + 1     3 y1 = max r + 1     4 count = the number of matching pixels
+ *                 5 sum_x = the sum of c (at most 512 * 512 * 511 / 2 = 66 977 792: it fits)     6 sum_y = the sum of r
+ *                 7 nearest: with `depth` = 1 the minimum over the matching pixels of the depth plane's 32-bit word, compared as uint32 -- the planes hold positive floats,
+ *                   whose words order as they do, so these are the bits of the smallest depth; with `depth` = 0: 0.
+ *               x0 .. y1 are a half-open box, [x0, x1) x [y0, y1); the centroid is (sum_x / count, sum_y / count).
+ *   empty       no matching pixel: all eight are zero.  count == 0 is the only "absent" test a consumer needs.
+ *   boxes       [N][slots][O][8] int32, env-major.
+ *   reproducible  every field is a minimum, a maximum or a sum of INTEGERS, taken with integer atomics in LDS: none depends on the order lanes arrive in, nor on the
+ *               floating-point flags of the build.  The same planes give the same bytes on every run.
+ *   invariant   after every entry point that draws the batched frames -- lcr_step, lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- the record is the
+ *               function above of that env's current planes.  No history and no reset rule: an auto-reset env shows its reset state, as its planes do.
+ *   ordering    the boxes kernel is the last launch behind the frame kernels -- frames, stack, cloud, grid, map, boxes -- on whatever stream they ran on; the event the
+ *               joining entry points wait for is recorded after it.
+ *   life        needs image observations and the segmentation plane, with `depth` = 1 the depth plane too; no plane is switched on silently.  Fixed for the life of the
+ *               handle: the same spec again does nothing, another spec is refused, naming both.
+ *   memory      one allocation: LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, the records, the same guard from the first 256-byte boundary at or behind their end (as the
+ *               heightmap has them).  Freed by lcr_destroy; LCR_ERR_OOM if it fails.
+ *   not in it   amodal boxes (the extent of occluded parts), oriented boxes, instances beyond the surface ids, a normalised float form (one torch expression over the
+ *               record), the recorder, and the boxes of an episode that has ended: there is no _terminal call, so the vector adapters refuse them. */
+#define LCR_BOXES_MAX_OBJECTS 16
+#define LCR_BOXES_MARKER 0x80000000u
+enum { LCR_BOXES_X0 = 0, LCR_BOXES_Y0 = 1, LCR_BOXES_X1 = 2, LCR_BOXES_Y1 = 3, LCR_BOXES_COUNT = 4, LCR_BOXES_SUM_X = 5, LCR_BOXES_SUM_Y = 6, LCR_BOXES_NEAREST = 7 };
+typedef struct lcr_object_boxes_spec {
+    uint32_t cameras;                           /* LCR_STACK_CAM_* bits, at least one */
+    int32_t n_objects;                          /* 1 .. LCR_BOXES_MAX_OBJECTS */
+    uint32_t objects[LCR_BOXES_MAX_OBJECTS];    /* [i < n_objects]: bits 1 .. 10 and LCR_BOXES_MARKER, not empty; [i >= n_objects] ignored (reported as 0) */
+    int32_t depth;                              /* 0 | 1: keep the nearest depth word of every record */
+} lcr_object_boxes_spec;
+typedef struct lcr_object_boxes_view {
+    int32_t enabled;                   /* 0: no boxes, everything below is 0 / NULL */
+    lcr_object_boxes_spec spec;        /* as enabled; the masks beyond n_objects are 0 */
+    int32_t slots, image_width, image_height;
+    const int32_t *boxes;              /* device, [N][slots][O][8] */
+    uint64_t bytes_per_env;            /* slots O 8 sizeof(int32_t) */
+} lcr_object_boxes_view;
+/* The checks lcr_enable_object_boxes makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field in the message -- cameras 0 or
+ * with unknown bits, n_objects outside 1 .. 16, an object that is empty or selects bit 0 or one of bits 11 .. 30 (named with its index), depth other than 0 / 1 */
+int lcr_object_boxes_check(const lcr_object_boxes_spec *spec);
+/* Switch the boxes on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without the segmentation plane, `depth` without the depth plane
+ * and a wrist bit without a wrist camera are refused (LCR_ERR_INVALID, naming what is missing); an allocation that fails is LCR_ERR_OOM.  Makes the records of the current
+ * planes. */
+int lcr_enable_object_boxes(lcr_sim *sim, const lcr_object_boxes_spec *spec);
+/* The records; waits (on the handle's stream) for frames and records still being made on the second stream, as every entry point but the step does. */
+int lcr_get_object_boxes(lcr_sim *sim, lcr_object_boxes_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */
