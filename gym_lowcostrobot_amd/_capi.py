@@ -54,6 +54,9 @@ BOXES_OBJECTS = {"floor": 1 << 1, "arm": 0x7F << 2, "cube": 1 << 9, "cube2": 1 <
                  **{f"link_{i}": 1 << (2 + i) for i in range(1, 7)}}
 BOXES_DEFAULT_OBJECTS = ("arm", "cube", "cube2", "marker")   # the same for every task: an object a task does not have gives empty records, the shape does not depend on the task
 BOXES_FIELDS = ("x0", "y0", "x1", "y1", "count", "sum_x", "sum_y", "nearest")
+# the surface normals (lcr_enable_normals): LCR_NORMALS_WORLD / LCR_NORMALS_CAMERA, the number of opaque boxes and the floats of one (centre, X, Y, Z, half-extents)
+NORMALS_FRAMES = {"world": 0, "camera": 1}
+NORMALS_BOXES, NORMALS_BOX_FLOATS = 9, 15
 LOOK_TASK_RGB = (0.5, 0.0, 0.0, 0.0, 0.0, 0.5, 0.0, 0.0, 1.0)   # the task's colours: cube, second cube (StackTwoCubes), target marker (PushCube / PickPlaceCube)
 
 LCR_OK, LCR_ERR_INVALID, LCR_ERR_NO_DEVICE, LCR_ERR_HIP, LCR_ERR_OOM, LCR_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -76,6 +79,7 @@ SYMBOLS = [
     "lcr_voxel_grid_check", "lcr_enable_voxel_grid", "lcr_get_voxel_grid",
     "lcr_heightmap_check", "lcr_enable_heightmap", "lcr_get_heightmap",
     "lcr_object_boxes_check", "lcr_enable_object_boxes", "lcr_get_object_boxes",
+    "lcr_normals_check", "lcr_enable_normals", "lcr_get_normals",
     "lcr_enable_obs_stack_planes", "lcr_get_obs_stack_planes",
 ]
 
@@ -855,6 +859,61 @@ class LcrObjectBoxesView(ctypes.Structure):
     ]
 
 
+class NormalsSpec(ctypes.Structure):
+    """lcr_normals_spec: cameras and frame of the surface normals (include/lcr.h)"""
+    _fields_ = [
+        ("cameras", ctypes.c_uint32),   # STACK_CAMERAS bits; 0 = every camera the handle has
+        ("frame", ctypes.c_int32),      # NORMALS_FRAMES
+    ]
+
+    def as_dict(self):
+        """cameras and frame as names"""
+        return {"cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b), "frame": {v: k for k, v in NORMALS_FRAMES.items()}[int(self.frame)]}
+
+    @classmethod
+    def from_any(cls, v, wrist=False):
+        """a NormalsSpec, True (the defaults), or a dict with some of cameras / frame.  `wrist`: the handle has a wrist camera (the default cameras are every camera the
+        handle has)"""
+        if isinstance(v, cls):
+            return v
+        if v is True:
+            v = {}
+        if not isinstance(v, dict):
+            raise ValueError(f"surface_normals must be None, True or a dict of cameras / frame, got {v!r}")
+        v = dict(v)
+        out = cls()
+        cams = v.pop("cameras", None)
+        if cams is None:
+            out.cameras = STACK_CAMERAS["front"] | STACK_CAMERAS["top"] | (STACK_CAMERAS["wrist"] if wrist else 0)
+        else:
+            if isinstance(cams, str) or not hasattr(cams, "__iter__") or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"surface_normals: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        frame = v.pop("frame", "world")
+        if not isinstance(frame, str) or frame not in NORMALS_FRAMES:
+            raise ValueError(f"surface_normals: frame must be 'world' or 'camera', got {frame!r}")
+        out.frame = NORMALS_FRAMES[frame]
+        if v:
+            raise ValueError(f"unknown surface_normals fields {sorted(v)}")
+        return out
+
+
+class LcrNormalsView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", NormalsSpec),                  # as enabled, cameras resolved
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("normals_front", ctypes.c_void_p),     # [N][H][W][4] int8, or NULL
+        ("normals_top", ctypes.c_void_p),
+        ("normals_wrist", ctypes.c_void_p),
+        ("boxes", ctypes.c_void_p),             # [9][15][N] float32
+        ("camera_pose", ctypes.c_void_p),       # [slots][13][N] float32
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -1004,6 +1063,9 @@ def load():
     L.lcr_object_boxes_check.argtypes = [ctypes.POINTER(ObjectBoxesSpec)]
     L.lcr_enable_object_boxes.argtypes = [vp, ctypes.POINTER(ObjectBoxesSpec)]
     L.lcr_get_object_boxes.argtypes = [vp, ctypes.POINTER(LcrObjectBoxesView)]
+    L.lcr_normals_check.argtypes = [ctypes.POINTER(NormalsSpec)]
+    L.lcr_enable_normals.argtypes = [vp, ctypes.POINTER(NormalsSpec)]
+    L.lcr_get_normals.argtypes = [vp, ctypes.POINTER(LcrNormalsView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

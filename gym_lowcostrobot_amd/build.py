@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblcr_hip.so")
-SOURCES = ["lcr_capi.hip", "lcr_kernels.hip", "lcr_kernels2.hip", "lcr_render.hip", "lcr_stack.hip", "lcr_cloud.hip", "lcr_cloud_fps.hip", "lcr_cloud_crop.hip", "lcr_voxel.hip", "lcr_heightmap.hip", "lcr_boxes.hip"]   # (bench.kernel_sha16 and the tools hash / compile these)
-HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
+SOURCES = ["lcr_capi.hip", "lcr_kernels.hip", "lcr_kernels2.hip", "lcr_render.hip", "lcr_stack.hip", "lcr_cloud.hip", "lcr_cloud_fps.hip", "lcr_cloud_crop.hip", "lcr_voxel.hip", "lcr_heightmap.hip", "lcr_boxes.hip", "lcr_normals.hip"]   # (bench.kernel_sha16 and the tools hash / compile these)
+HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_normals.h", "lcr_opaque_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
 # -ffast-math: the kernels carry no NaN/inf/signed-zero semantics (the -0.0 sparse reward is built from its bit pattern,
 # the fp64 reset sampling uses explicitly rounded __dmul_rn/__dadd_rn); -fno-slp-vectorize: packed-f32 formation by the
 # SLP vectoriser costs more moves than it saves here (measured on MI355X: 0.340 ms -> 0.286 ms per 65 536-env step).
@@ -60,6 +60,9 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          ("lcr_heightmap.hip", "lcr_heightmap.o", []),
          # the object boxes (lcr_enable_object_boxes): one kernel, integer arithmetic throughout; a unit of its own
          ("lcr_boxes.hip", "lcr_boxes.o", []),
+         # the surface normals (lcr_enable_normals): one kernel; a unit of its own.  The project's flags: the point, the box coordinates and the quantisation
+         # its header pins to the bit are kept from -ffast-math inside the source (normal_point, pinned_dot, quantise)
+         ("lcr_normals.hip", "lcr_normals.o", []),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),

@@ -18,6 +18,7 @@
 #include "lcr_voxel.h"
 #include "lcr_heightmap.h"
 #include "lcr_boxes.h"
+#include "lcr_normals.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -213,6 +214,11 @@ struct lcr_sim {
     lcr_object_boxes_spec boxes_spec;  // as enabled, the masks beyond n_objects zero
     LcrBoxes boxes;                    // the arguments of their kernel: a view of the handle's own planes
     void *boxes_mem;
+    // the surface normals (lcr_enable_normals): one allocation -- guard, then per slot plane and guard, boxes, camera poses --, fixed for the life of the handle
+    bool normals_on;
+    lcr_normals_spec normals_spec;     // as enabled, cameras resolved
+    LcrNormals normals;                // the arguments of their kernel (the cameras and the pose snapshot are set per launch)
+    void *normals_mem;
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -287,9 +293,20 @@ static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, con
     return lcr_launch_heightmap(A, stream);
 }
 
+// the normals kernel, behind the frame kernels (and every other observation kernel) on their stream: the planes of P's envs from the frames just drawn, with the cameras that
+// drew them and the boxes and the wrist pose from P's qpos, as launch_cloud passes them
+static int launch_normals(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
+    LcrNormals A = s->normals;
+    A.front = s->cam_front; A.top = s->cam_top;
+    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
+    A.qpos = P.qpos;
+    return lcr_launch_normals(A, stream);
+}
+
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
 // handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, on
-// one with a heightmap its kernel, and on one with object boxes their kernel last (it reads the planes alone: no camera, no look, no pose)
+// one with a heightmap its kernel, on one with object boxes their kernel (it reads the planes alone: no camera, no look, no pose), and on one with surface normals their
+// kernel last
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
@@ -297,6 +314,7 @@ static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     if (s->voxel_on) LAUNCHCHK("voxel-grid kernel", launch_voxel(s, P, stream, look));
     if (s->height_on) LAUNCHCHK("heightmap kernel", launch_heightmap(s, P, stream, look));
     if (s->boxes_on) LAUNCHCHK("object-boxes kernel", lcr_launch_object_boxes(s->boxes, stream));
+    if (s->normals_on) LAUNCHCHK("normals kernel", launch_normals(s, P, stream, look));
     return LCR_OK;
 }
 
@@ -801,6 +819,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->voxel_mem) (void)hipFree(s->voxel_mem);
     if (s->height_mem) (void)hipFree(s->height_mem);
     if (s->boxes_mem) (void)hipFree(s->boxes_mem);
+    if (s->normals_mem) (void)hipFree(s->normals_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -2419,6 +2438,94 @@ int lcr_get_object_boxes(lcr_sim *s, lcr_object_boxes_view *out) {
     out->image_height = s->dev.img_h;
     out->boxes = s->boxes.out;
     out->bytes_per_env = (uint64_t)s->boxes.slots * s->boxes.n_objects * 8 * sizeof(int32_t);
+    return LCR_OK;
+}
+
+// ---- the surface normals ----
+
+int lcr_normals_check(const lcr_normals_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be 0 (every camera the handle has) or a mask of 1 (front), 2 (top) and 4 (wrist), got %u", spec->cameras);
+    if (spec->frame != LCR_NORMALS_WORLD && spec->frame != LCR_NORMALS_CAMERA) return fail(LCR_ERR_INVALID, "frame must be 0 (world) or 1 (camera), got %d", spec->frame);
+    return LCR_OK;
+}
+
+int lcr_enable_normals(lcr_sim *s, const lcr_normals_spec *spec) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_normals_check(spec)) return rc;
+    SIMCHK(s);
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to give normals to");
+    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
+    if ((s->planes & both) != both)
+        return fail(LCR_ERR_INVALID, "the surface normals need both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the normals): %s",
+                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
+    lcr_normals_spec sp = *spec;
+    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the normals)");
+    if (s->normals_on) {
+        if (sp.cameras == s->normals_spec.cameras && sp.frame == s->normals_spec.frame) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "surface normals (cameras %u, frame %d) are enabled already and fixed for the life of the handle: asked for cameras %u, frame %d",
+                    s->normals_spec.cameras, s->normals_spec.frame, sp.cameras, sp.frame);
+    }
+    LcrNormals A{};
+    auto slot = [&A](int cam, const unsigned char *seg, const float *depth) { A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.slots++; };
+    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front);
+    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top);
+    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth);
+    const size_t N = (size_t)s->dev.n, plane = N * s->dev.img_w * s->dev.img_h * 4;
+    // guard, then per slot the plane and a guard (include/lcr.h: LCR_WRIST_GUARD), then the boxes and the camera poses
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    size_t o_plane[3] = {0, 0, 0};
+    for (int i = 0; i < A.slots; i++) { o_plane[i] = C.take(plane); C.skip(LCR_WRIST_GUARD); }
+    const size_t guarded = C.off;
+    const size_t o_boxes = C.take((size_t)LCR_NORMALS_BOXES * LCR_NORMALS_BOX_FLOATS * N * sizeof(float));
+    const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
+    const size_t off = C.off;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the surface normals failed: %s", off, hipGetErrorString(e));
+    char *base = (char *)mem;
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.frame = sp.frame;
+    A.ncube = s->dev.task == 4 ? 2 : 1;
+    for (int i = 0; i < A.slots; i++) A.out[i] = (unsigned *)(base + o_plane[i]);
+    A.boxes = (float *)(base + o_boxes);
+    A.pose = (float *)(base + o_pose);
+    A.mount = s->wrist.mount;
+    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
+    s->normals = A;
+    if (!rc) rc = launch_normals(s, s->dev, s->stream, nullptr);
+    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->normals = LcrNormals{}; return fail(LCR_ERR_UNSUPPORTED, "the normals kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
+    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (rc) { (void)hipFree(mem); s->normals = LcrNormals{}; return fail(LCR_ERR_HIP, "making the surface normals failed: %s", hipGetErrorString((hipError_t)rc)); }
+    s->normals_mem = mem;
+    s->normals_spec = sp;
+    s->normals_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_normals(lcr_sim *s, lcr_normals_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the planes are made behind the frames, on the second stream after a step: the handle's stream waits for them here)
+    memset(out, 0, sizeof *out);
+    if (!s->normals_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->normals_spec;
+    out->slots = s->normals.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    for (int i = 0; i < s->normals.slots; i++) {
+        const int8_t *p = (const int8_t *)s->normals.out[i];
+        if (s->normals.cam[i] == LCR_CLOUD_CAM_FRONT) out->normals_front = p;
+        else if (s->normals.cam[i] == LCR_CLOUD_CAM_TOP) out->normals_top = p;
+        else out->normals_wrist = p;
+    }
+    out->boxes = s->normals.boxes;
+    out->camera_pose = s->normals.pose;
+    out->bytes_per_env = (uint64_t)s->normals.slots * s->dev.img_w * s->dev.img_h * 4;
     return LCR_OK;
 }
 

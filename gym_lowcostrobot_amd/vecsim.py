@@ -99,6 +99,7 @@ class VecSim:
         voxel_grid=None,
         heightmap=None,
         object_boxes=None,
+        surface_normals=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -213,6 +214,22 @@ class VecSim:
             if object_boxes.depth and "depth" not in image_planes:
                 raise ValueError(f"object_boxes: depth=True keeps the nearest depth of every record and needs the depth plane: image_planes=('depth', 'segmentation') (got {image_planes!r})")
             check(self.L.lcr_object_boxes_check(ctypes.byref(object_boxes)))
+        # the surface normals (lcr_enable_normals): None / False = none, True = the defaults (every camera the handle has, world frame), or a dict with some of cameras /
+        # frame ("world" | "camera").  Checked here and by the library without a handle (lcr_normals_check), before it is asked for a device.  They are made of the depth and
+        # the segmentation plane: neither is switched on silently
+        if surface_normals is None or surface_normals is False:
+            surface_normals = None
+        else:
+            if observation_mode == "state":
+                raise ValueError("surface_normals needs image observations: observation_mode 'image' or 'both'")
+            surface_normals = _capi.NormalsSpec.from_any(surface_normals, wrist=wrist_camera is not None)
+            if surface_normals.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("surface_normals: cameras selects 'wrist', but no wrist_camera is given")
+            for plane in _capi.IMAGE_PLANES:
+                if plane not in image_planes:
+                    raise ValueError(f"surface_normals is made of the depth and the segmentation plane: the {plane} plane is missing, pass both, "
+                                     f"image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_normals_check(ctypes.byref(surface_normals)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -450,6 +467,21 @@ class VecSim:
                 raise
             self.object_boxes_spec = object_boxes.as_dict()
             self.object_boxes = DeviceArray(self, bv.boxes, (N, int(bv.slots), int(bv.spec.n_objects), 8), np.int32)
+        # the surface normals: (N, H, W, 4) int8 per selected camera -- rint(127 n) and the face code --, the nine boxes and the camera poses the kernel used.  A handle
+        # without them has none of these attributes
+        if surface_normals is not None:   # (behind look, wrist camera and planes; independent of every other observation unit)
+            try:
+                check(self.L.lcr_enable_normals(self.handle, ctypes.byref(surface_normals)))
+                nv = _capi.LcrNormalsView()
+                check(self.L.lcr_get_normals(self.handle, ctypes.byref(nv)))
+            except Exception:
+                self.close()
+                raise
+            self.normals_spec = nv.spec.as_dict()
+            for cam in self.normals_spec["cameras"]:
+                setattr(self, "normals_" + cam, DeviceArray(self, getattr(nv, "normals_" + cam), (N, int(nv.image_height), int(nv.image_width), 4), np.int8))
+            self.normals_boxes = DeviceArray(self, nv.boxes, (_capi.NORMALS_BOXES, _capi.NORMALS_BOX_FLOATS, N), np.float32)
+            self.normals_pose = DeviceArray(self, nv.camera_pose, (int(nv.slots), 13, N), np.float32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -488,7 +520,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack, point cloud, voxel grid, heightmap, object boxes): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud, voxel grid, heightmap, object boxes, surface normals): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -728,6 +760,8 @@ class VecSim:
                 obs["heightmap"] = self.heightmap.numpy()
             if self.object_boxes is not None:
                 obs["object_boxes"] = self.object_boxes.numpy()
+            for cam in getattr(self, "normals_spec", {"cameras": ()})["cameras"]:
+                obs["normals_" + cam] = getattr(self, "normals_" + cam).numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

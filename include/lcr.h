@@ -942,6 +942,77 @@ int lcr_enable_object_boxes(lcr_sim *sim, const lcr_object_boxes_spec *spec);
 /* The records; waits (on the handle's stream) for frames and records still being made on the second stream, as every entry point but the step does. */
 int lcr_get_object_boxes(lcr_sim *sim, lcr_object_boxes_view *out);
 
+/* == Surface normals: optional device buffers per handle, one plane `normals` [N][H][W][4] int8 per selected camera, that the library keeps current behind the frame kernels
+ * -- per pixel the unit normal of the surface the pixel shows and the face of the box it belongs to.  For point clouds with normals (grasp-pose networks gather them through
+ * the cloud's `source`), RGB-D-N inputs, and contact-direction or "which face of the cube" labels.  The normal is EXACT, not estimated from depth gradients: every opaque
+ * surface is the floor or one of nine oriented boxes, the segmentation byte says which, the depth plane gives the point, and the pose snapshot the frames were drawn from
+ * gives the box frames.  One streaming kernel, in stream order, without a host round trip.  Off by default: without lcr_enable_normals no byte, state, output or kernel of
+ * the handle changes.
+ *   inputs      the segmentation and depth planes of the selected camera slots at the configured size [H][W] (`cameras`: LCR_STACK_CAM_* bits, 0 = every camera the handle
+ *               has; slots in the order front, top, wrist, as the cloud has them; the wrist bit on a handle without a wrist camera is refused), the camera that drew each
+ *               slot (the env's look variant's; the wrist pose of the step) and the pose snapshot `qpos` the frames were drawn from.
+ *   element     [..., 0:3] the normal n as rint(127 n), [..., 3] the face code w:
+ *                 w = 0                    no surface (sky): four zeros
+ *                 w = 1 + 2 axis + side    face `axis` (0 X, 1 Y, 2 Z) of the box's own frame, `side` 1 on the negative side: 1 .. 6
+ *                 the floor is w = 5, the + Z face of the world: (0, 0, 127, 5) in the world frame
+ *   boxes       the nine opaque boxes in the order of the surface ids 2 .. 10 (base_link, link_1 .. link_6, the cube, the second cube), placed as the frame kernels place
+ *               them: centre c, axes X, Y, Z (A_0, A_1, A_2) and half-extents h in float32, reported as `boxes` [9][15][N] (c, X, Y, Z, h) exactly as the kernel used them;
+ *               all 15 are zero for a second cube the task does not have.
+ *   the rule    for pixel (row, px) of a slot with id i = seg & 0x7F.  The marker bit is ignored: the normal is that of the opaque surface the id names.
+ *                 i = 0 or i > 10   four zeros
+ *                 i = 1             world + z, w = 5
+ *                 i = 2 .. 10       box i - 2:
+ *                   p     the pinned point of the crop box, the voxel grid and the heightmap: per axis fmaf(t, fmaf(sx, X, fmaf(sy, Y, -Z)), ro) with sx = (px + 0.5 -
+ *                         W / 2) s and sy = -((row + 0.5 - H / 2) s) one rounded float32 multiply each, t the depth word as stored, and ro, X, Y, Z, s the reported
+ *                         `camera_pose` of the slot
+ *                   u     = p - c: one float32 subtraction per axis
+ *                   l_k   = fmaf(u.x, A_k.x, fmaf(u.y, A_k.y, u.z * A_k.z)) for k = 0, 1, 2
+ *                   e_k   = |l_k| - h_k: one float32 subtraction
+ *                   axis  the largest e_k, ties to the lowest k: e_0 >= e_1 && e_0 >= e_2 ? 0 : e_1 >= e_2 ? 1 : 2
+ *                   side  negative (1) iff l_axis < 0.0f
+ *                   n     = +- A_axis
+ *   quantised   each of the at most 55 vectors per (env, slot) -- the floor and six faces of nine boxes -- once: clamp((int)rintf(127.0f * component), -127, 127), rintf
+ *               to nearest even.  `frame` LCR_NORMALS_WORLD: the component of n itself.  LCR_NORMALS_CAMERA: first dot(n, C) = fmaf(n.x, C.x, fmaf(n.y, C.y, n.z * C.z))
+ *               for C the slot's camera axis X, Y, Z in turn -- the axes the cloud, the grid and the map use, those of the camera that drew the pixel.  The axes of a
+ *               cube are those of its quaternion as stored; the clamp keeps a component that a quaternion off the unit sphere by rounding would carry past 127.
+ *   reproducible  every word is a function of its own pixel, the boxes and the pose: nothing depends on the order lanes arrive in, there are no atomics, and every rounded
+ *               intermediate above is one float32 operation whatever the floating-point flags of the build.
+ *   depth_far   a depth clipped at depth_far gives the face of the CLIPPED point, which need not be the face the ray entered by: depth_far belongs beyond the scene, as
+ *               its default (10 m) is.  There is no special case.
+ *   invariant   after every entry point that draws the batched frames -- lcr_step, lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- each plane is the
+ *               function above of that env's current planes, boxes and pose.  No history and no reset rule: an auto-reset env shows its reset state, as its planes do.
+ *   ordering    the normals kernel is the last launch behind the frame kernels -- frames, stack, cloud, grid, map, boxes, normals -- on whatever stream they ran on; the
+ *               event the joining entry points wait for is recorded after it.
+ *   life        needs image observations and BOTH planes, neither switched on silently (lcr_enable_image_planes stays what it is: normals are no third plane bit).  Fixed
+ *               for the life of the handle: the same spec again does nothing, another spec is refused, naming both.
+ *   memory      4 bytes per pixel and camera (307 200 bytes per env and camera at 240 x 320); the caller chooses it.  One allocation: LCR_WRIST_GUARD bytes of
+ *               LCR_WRIST_GUARD_BYTE, then per slot the plane and the same guard from the first 256-byte boundary at or behind its end (every plane lies between two guard
+ *               regions, as the wrist buffers do), then boxes and camera_pose.  Freed by lcr_destroy; LCR_ERR_OOM if it fails.
+ *   not in it   float output (one torch expression, x[..., :3].float() * (1 / 127)), terminal planes (there is no _terminal call, so the vector adapters refuse them), the
+ *               recorder, a normals channel of the stack or the cloud, and the marker's own faces. */
+enum { LCR_NORMALS_WORLD = 0, LCR_NORMALS_CAMERA = 1 };
+typedef struct lcr_normals_spec {
+    uint32_t cameras;                  /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+    int32_t frame;                     /* LCR_NORMALS_WORLD | LCR_NORMALS_CAMERA */
+} lcr_normals_spec;
+typedef struct lcr_normals_view {
+    int32_t enabled;                   /* 0: no normals, everything below is 0 / NULL */
+    lcr_normals_spec spec;             /* as enabled, cameras resolved */
+    int32_t slots, image_width, image_height;
+    const int8_t *normals_front, *normals_top, *normals_wrist;   /* device, [N][H][W][4]; NULL for a camera that is not selected */
+    const float *boxes;                /* device, [9][15][N]: c, X, Y, Z, h of the nine boxes */
+    const float *camera_pose;          /* device, [slots][13][N]: ro, X, Y, Z, s */
+    uint64_t bytes_per_env;            /* slots H W 4 */
+} lcr_normals_view;
+/* The checks lcr_enable_normals makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID with the field in the message -- cameras with unknown
+ * bits, frame other than 0 / 1 */
+int lcr_normals_check(const lcr_normals_spec *spec);
+/* Switch the normals on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without both planes (naming the missing one) and a wrist bit
+ * without a wrist camera are refused (LCR_ERR_INVALID); an allocation that fails is LCR_ERR_OOM.  Makes the planes of the current frames. */
+int lcr_enable_normals(lcr_sim *sim, const lcr_normals_spec *spec);
+/* The planes; waits (on the handle's stream) for frames and normals still being made on the second stream, as every entry point but the step does. */
+int lcr_get_normals(lcr_sim *sim, lcr_normals_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */
