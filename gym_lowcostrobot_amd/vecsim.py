@@ -713,7 +713,7 @@ class VecSim:
         nb = int(np.prod(row_shape)) * arr.dtype.itemsize
         out = np.empty((len(rows),) + row_shape, arr.dtype)
         for i, r in enumerate(rows):
-            check(self.L.lcr_memcpy_d2h(self.handle, _vp(out[i]), ctypes.c_void_p(arr.ptr + int(r) * nb), nb))
+            check(self.L.lcr_memcpy_d2h(self.handle, _vp(out[i:i + 1]), ctypes.c_void_p(arr.ptr + int(r) * nb), nb))   # (a slice: out[i] of an (N,) array is a scalar, not a view)
         return out
 
     def calibrate_copy(self, n_floats):

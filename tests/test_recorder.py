@@ -53,3 +53,23 @@ def test_record_wrapper_fixed_length(tmp_path):
         env.step(np.zeros(5, np.float32))
     env.close()
     assert len(env.files) == 1 and recorder.load_episode(env.files[0])["action"].shape == (3, 5)
+
+
+def test_read_rows_takes_rows_of_any_rank():
+    """VecSim.read_rows copies one row at a time; a row of an (N,) array (the count of a point cloud, a flag) is a single element, and a row of (N, H, W) a plane"""
+    import ctypes
+
+    from gym_lowcostrobot_amd.vecsim import DeviceArray, VecSim
+
+    class _HostLib:   # lcr_memcpy_d2h over host memory
+        @staticmethod
+        def lcr_memcpy_d2h(handle, dst, src, nbytes):
+            ctypes.memmove(dst, src, nbytes)
+            return 0
+
+    sim = VecSim.__new__(VecSim)
+    sim.L, sim.handle = _HostLib, None
+    for shape in ((10,), (10, 3), (10, 2, 4)):
+        src = np.arange(int(np.prod(shape)), dtype=np.int32).reshape(shape)
+        got = sim.read_rows(DeviceArray(sim, src.ctypes.data, shape, np.int32), [9, 0, 4])
+        np.testing.assert_array_equal(got, src[[9, 0, 4]])
