@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblcr_hip.so")
 SOURCES = ["lcr_capi.hip", "lcr_kernels.hip", "lcr_kernels2.hip", "lcr_render.hip", "lcr_stack.hip", "lcr_cloud.hip", "lcr_cloud_fps.hip", "lcr_cloud_crop.hip", "lcr_voxel.hip", "lcr_heightmap.hip", "lcr_boxes.hip", "lcr_normals.hip"]   # (bench.kernel_sha16 and the tools hash / compile these)
-HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_normals.h", "lcr_opaque_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
+HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_obs_cameras.inc.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_normals.h", "lcr_opaque_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
 # -ffast-math: the kernels carry no NaN/inf/signed-zero semantics (the -0.0 sparse reward is built from its bit pattern,
 # the fp64 reset sampling uses explicitly rounded __dmul_rn/__dadd_rn); -fno-slp-vectorize: packed-f32 formation by the
 # SLP vectoriser costs more moves than it saves here (measured on MI355X: 0.340 ms -> 0.286 ms per 65 536-env step).
@@ -50,18 +50,18 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          # the distance its header pins to the bit is kept from -ffast-math inside the source (fps_dist), the rest is the code the strided kernel runs
          ("lcr_cloud_fps.hip", "lcr_cloud_fps.o", []),
          # the cloud inside a crop box (lcr_enable_point_cloud_cropped): a strided kernel with and one without colours and four farthest-point kernels, a unit of its own.
-         # The project's flags: the point its header pins to the bit is kept from -ffast-math inside the source (crop_point)
+         # The project's flags: the point its header pins to the bit is kept from -ffast-math inside the source (pinned_point, lcr_cloud_dev.h)
          ("lcr_cloud_crop.hip", "lcr_cloud_crop.o", []),
          # the voxel grid (lcr_enable_voxel_grid): a kernel per element type, with and without colours, each also in a build with 128 KiB of LDS; a unit of its own.  The
-         # project's flags: the point and the voxel its header pins to the bit are kept from -ffast-math inside the source (voxel_point, voxel_axis)
+         # project's flags: the point and the voxel its header pins to the bit are kept from -ffast-math inside the source (pinned_point, cell_axis: lcr_cloud_dev.h)
          ("lcr_voxel.hip", "lcr_voxel.o", []),
          # the heightmap (lcr_enable_heightmap): a kernel with and one without colours, each with one and with four rounds of the scan in flight; a unit of its own.  The
-         # project's flags: the point, the cell and the height its header pins to the bit are kept from -ffast-math inside the source (height_point, height_axis, height_word)
+         # project's flags: the point, the cell and the height its header pins to the bit are kept from -ffast-math inside the source (pinned_point, cell_axis: lcr_cloud_dev.h; height_word)
          ("lcr_heightmap.hip", "lcr_heightmap.o", []),
          # the object boxes (lcr_enable_object_boxes): one kernel, integer arithmetic throughout; a unit of its own
          ("lcr_boxes.hip", "lcr_boxes.o", []),
          # the surface normals (lcr_enable_normals): one kernel; a unit of its own.  The project's flags: the point, the box coordinates and the quantisation
-         # its header pins to the bit are kept from -ffast-math inside the source (normal_point, pinned_dot, quantise)
+         # its header pins to the bit are kept from -ffast-math inside the source (pinned_point, lcr_cloud_dev.h; pinned_dot, quantise)
          ("lcr_normals.hip", "lcr_normals.o", []),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)

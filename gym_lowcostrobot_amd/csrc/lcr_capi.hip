@@ -254,14 +254,20 @@ static int launch_stack(lcr_sim *s, hipStream_t stream, const unsigned char *fla
     return lcr_launch_obs_stack(A, stream);
 }
 
-// the cloud kernel, behind the frame kernels (and the stack kernel) on their stream: the cloud of P's envs from the frames just drawn, with the cameras that drew them --
-// the handle's or, with a look, those of the envs' variants (`look` as in look_args) -- and the wrist pose from P's qpos, the pose snapshot the wrist frames were drawn from
-// `view` (or null: the handle's own buffers): the cloud's arguments with planes, frames, outputs and n of a view of some envs (lcr_point_cloud_terminal)
-static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const LcrCloud *view = nullptr) {
-    LcrCloud A = view ? *view : s->cloud;
+// What every kernel of a depth-plane observation (LcrCloud, LcrVoxel, LcrHeightmap, LcrNormals) is told per launch: the cameras that drew the frames of P's envs -- the
+// handle's or, with a look, those of the envs' variants (`look` as in look_args) -- and P's qpos, the pose snapshot the wrist frames were drawn from
+template <class Args>
+static Args with_cameras(const lcr_sim *s, const LcrDev &P, const int *look, Args A) {
     A.front = s->cam_front; A.top = s->cam_top;
     if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
     A.qpos = P.qpos;
+    return A;
+}
+
+// the cloud kernel, behind the frame kernels (and the stack kernel) on their stream: the cloud of P's envs from the frames just drawn (with_cameras).
+// `view` (or null: the handle's own buffers): the cloud's arguments with planes, frames, outputs and n of a view of some envs (lcr_point_cloud_terminal)
+static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const LcrCloud *view = nullptr) {
+    const LcrCloud A = with_cameras(s, P, look, view ? *view : s->cloud);
     if (s->cloud_crop_on) {   // (a handle without a crop launches what it launched before there was one)
         LcrCloudCrop B{};
         B.c = A;
@@ -273,35 +279,11 @@ static int launch_cloud(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     return lcr_launch_point_cloud(A, stream);
 }
 
-// the grid kernel, behind the frame kernels (the stack kernel and the cloud kernel) on their stream: the grid of P's envs from the frames just drawn, with the cameras that
-// drew them and the wrist pose from P's qpos, as launch_cloud passes them
-static int launch_voxel(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
-    LcrVoxel A = s->voxel;
-    A.front = s->cam_front; A.top = s->cam_top;
-    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
-    A.qpos = P.qpos;
-    return lcr_launch_voxel_grid(A, stream);
-}
-
-// the heightmap kernel, behind the frame kernels (the stack, the cloud and the grid kernel) on their stream: the map of P's envs from the frames just drawn, with the cameras
-// that drew them and the wrist pose from P's qpos, as launch_cloud passes them
-static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
-    LcrHeightmap A = s->height;
-    A.front = s->cam_front; A.top = s->cam_top;
-    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
-    A.qpos = P.qpos;
-    return lcr_launch_heightmap(A, stream);
-}
-
-// the normals kernel, behind the frame kernels (and every other observation kernel) on their stream: the planes of P's envs from the frames just drawn, with the cameras that
-// drew them and the boxes and the wrist pose from P's qpos, as launch_cloud passes them
-static int launch_normals(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) {
-    LcrNormals A = s->normals;
-    A.front = s->cam_front; A.top = s->cam_top;
-    if (s->look_K) { const LcrLook LK = look_args(s, P, look); A.var = LK.var; A.variant = LK.variant; }
-    A.qpos = P.qpos;
-    return lcr_launch_normals(A, stream);
-}
+// the grid, the heightmap and the normals kernel, in this order behind the frame kernels (the stack kernel and the cloud kernel) on their stream: the grid, the map and the
+// normal planes of P's envs from the frames just drawn (with_cameras; the normals' boxes come from P's qpos too)
+static int launch_voxel(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) { return lcr_launch_voxel_grid(with_cameras(s, P, look, s->voxel), stream); }
+static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) { return lcr_launch_heightmap(with_cameras(s, P, look, s->height), stream); }
+static int launch_normals(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) { return lcr_launch_normals(with_cameras(s, P, look, s->normals), stream); }
 
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
 // handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, on
@@ -316,6 +298,62 @@ static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     if (s->boxes_on) LAUNCHCHK("object-boxes kernel", lcr_launch_object_boxes(s->boxes, stream));
     if (s->normals_on) LAUNCHCHK("normals kernel", launch_normals(s, P, stream, look));
     return LCR_OK;
+}
+
+// ---- the set-up path the observations made of the depth and segmentation planes share (the point cloud, the voxel grid, the heightmap, the object boxes, the normals) ----
+
+// What every observation that needs BOTH planes asks of the handle, behind its argument checks: frames, both planes, and a wrist camera where `*cameras` selects one;
+// *cameras == 0 becomes every camera the handle has.  The words name the observation in the refusals: there are no frames `of` ("to make a voxel grid of"), `needs` ("the
+// voxel grid needs") both planes, enabled before `it` ("the grid").  (The object boxes need the segmentation plane alone and keep their own checks.)
+static int planes_ready(const lcr_sim *s, uint32_t *cameras, const char *of, const char *needs, const char *it) {
+    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames %s", of);
+    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
+    if ((s->planes & both) != both)
+        return fail(LCR_ERR_INVALID, "%s both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before %s): %s", needs, it,
+                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
+    if (*cameras == 0) *cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if ((*cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on)
+        return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and %s)", it);
+    return LCR_OK;
+}
+
+// a selected camera: where its pose comes from (LCR_CLOUD_CAM_*) and the planes and frames it draws.  The argument structs differ (the normals take no frames, the object
+// boxes no camera and the depth as words), so every enable copies the fields its kernel has out of these
+struct ObsSource {
+    int cam;
+    const unsigned char *seg;
+    const float *depth;
+    const unsigned char *rgb;
+};
+// the cameras `cameras` selects, in slot order front, top, wrist; returns how many
+static int sources(const lcr_sim *s, uint32_t cameras, ObsSource (&src)[3]) {
+    int n = 0;
+    if (cameras & LCR_STACK_CAM_FRONT) src[n++] = ObsSource{LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front};
+    if (cameras & LCR_STACK_CAM_TOP) src[n++] = ObsSource{LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top};
+    if (cameras & LCR_STACK_CAM_WRIST) src[n++] = ObsSource{LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img};
+    return n;
+}
+
+// The tail of every enable: the allocation C lays out (*mem), its first `guarded` bytes filled with the guard byte and the rest zeroed, then `first(base)` -- which points the
+// kernel's arguments into the allocation, puts on the handle what the launch reads there and returns the first launch's status -- and a wait for it.  On a failure the
+// allocation is freed and `undo()` takes back what first() put on the handle: LCR_ERR_OOM, LCR_ERR_HIP, or LCR_ERR_UNSUPPORTED for arguments the launcher refuses (a
+// negative status), whose message is the caller's to word.  `what` ("the voxel grid") names the observation in the other two
+template <class First, class Undo>
+static int bring_up(lcr_sim *s, const Carver &C, size_t guarded, const char *what, void **mem, First first, Undo undo) {
+    hipError_t e = hipMalloc(mem, C.off);
+    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for %s failed: %s", C.off, what, hipGetErrorString(e));
+    char *base = (char *)*mem;
+    int rc = (int)hipMemsetAsync(base, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
+    if (!rc && C.off > guarded) rc = (int)hipMemsetAsync(base + guarded, 0, C.off - guarded, s->stream);
+    if (!rc) rc = first(base);
+    if (rc < 0) (void)hipStreamSynchronize(s->stream);   // (the memsets are on their way: the allocation is not freed under them)
+    else if (!rc) rc = (int)hipStreamSynchronize(s->stream);
+    if (!rc) return LCR_OK;
+    (void)hipFree(*mem);
+    *mem = nullptr;
+    undo();
+    if (rc < 0) return LCR_ERR_UNSUPPORTED;   // (the caller says what the kernel is not built for)
+    return fail(LCR_ERR_HIP, "making %s failed: %s", what, hipGetErrorString((hipError_t)rc));
 }
 
 // the wrist camera's mount with the ray scale of a frame `height` rows high (s = 2 tan(fovy / 2) / height in fp64, then rounded)
@@ -1917,15 +1955,9 @@ int lcr_enable_point_cloud_cropped(lcr_sim *s, const lcr_point_cloud_spec *spec,
         if (int rc = lcr_point_cloud_crop_check(crop)) return rc;
     const lcr_point_cloud_crop cr = crop ? *crop : lcr_point_cloud_crop{};
     SIMCHK(s);
-    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a point cloud of");
-    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
-    if ((s->planes & both) != both)
-        return fail(LCR_ERR_INVALID, "the point cloud needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the cloud): %s",
-                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
     lcr_point_cloud_spec sp = *spec;
-    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (int rc = planes_ready(s, &sp.cameras, "to make a point cloud of", "the point cloud needs", "the cloud")) return rc;
     if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
-    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the cloud)");
     if (s->cloud_on) {
         // (the boxes compare as float32 values: the comparisons the kernel makes with them are the same then; no side is a NaN)
         bool same_crop = s->cloud_crop_on == (crop != nullptr);
@@ -1946,12 +1978,9 @@ int lcr_enable_point_cloud_cropped(lcr_sim *s, const lcr_point_cloud_spec *spec,
                     s->cloud_spec.colors, cloud_mode_name(s->cloud_sampling.mode), s->cloud_sampling.pool, sp.points, sp.cameras, sp.ids, sp.colors, cloud_mode_name(sm.mode), sm.pool);
     }
     LcrCloud A{};
-    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
-        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
-    };
-    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
-    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
-    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.cam[i] = src[i].cam; A.seg[i] = src[i].seg; A.depth[i] = src[i].depth; A.rgb[i] = src[i].rgb; }
     const size_t N = (size_t)s->dev.n, P = (size_t)sp.points, Cn = sp.colors ? 6 : 3;
     // guard, points, guard (include/lcr.h: LCR_WRIST_GUARD), then count, source and the camera poses
     Carver C;
@@ -1962,32 +1991,25 @@ int lcr_enable_point_cloud_cropped(lcr_sim *s, const lcr_point_cloud_spec *spec,
     const size_t o_cnt = C.take(N * sizeof(int));
     const size_t o_src = C.take(N * P * sizeof(int));
     const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
-    const size_t off = C.off;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, off);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the point cloud failed: %s", off, hipGetErrorString(e));
-    char *base = (char *)mem;
     A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
     A.points = sp.points; A.channels = (int)Cn; A.ids = sp.ids;
-    A.out = (float *)(base + o_pts);
-    A.count = (int *)(base + o_cnt);
-    A.source = (int *)(base + o_src);
-    A.pose = (float *)(base + o_pose);
     A.mount = s->wrist.mount;
-    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
-    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
-    s->cloud = A;
-    s->cloud_sampling = sm;
-    s->cloud_crop_on = crop != nullptr;
-    s->cloud_crop = cr;
-    const auto undo = [s, mem] {
-        (void)hipFree(mem);
-        s->cloud = LcrCloud{}; s->cloud_sampling = lcr_point_cloud_sampling{}; s->cloud_crop_on = false; s->cloud_crop = lcr_point_cloud_crop{};
-    };
-    if (!rc) rc = launch_cloud(s, s->dev, s->stream, nullptr);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); undo(); return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
-    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { undo(); return fail(LCR_ERR_HIP, "making the point cloud failed: %s", hipGetErrorString((hipError_t)rc)); }
+    void *mem = nullptr;
+    const int rc = bring_up(s, C, guarded, "the point cloud", &mem,
+        [&](char *base) {
+            A.out = (float *)(base + o_pts);
+            A.count = (int *)(base + o_cnt);
+            A.source = (int *)(base + o_src);
+            A.pose = (float *)(base + o_pose);
+            s->cloud = A;
+            s->cloud_sampling = sm;
+            s->cloud_crop_on = crop != nullptr;
+            s->cloud_crop = cr;
+            return launch_cloud(s, s->dev, s->stream, nullptr);
+        },
+        [s] { s->cloud = LcrCloud{}; s->cloud_sampling = lcr_point_cloud_sampling{}; s->cloud_crop_on = false; s->cloud_crop = lcr_point_cloud_crop{}; });
+    if (rc == LCR_ERR_UNSUPPORTED) return fail(LCR_ERR_UNSUPPORTED, "the point-cloud kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H);
+    if (rc) return rc;
     s->cloud_mem = mem;
     s->cloud_spec = sp;
     s->cloud_on = true;
@@ -2124,16 +2146,10 @@ int lcr_enable_voxel_grid(lcr_sim *s, const lcr_voxel_grid_spec *spec) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_voxel_grid_check(spec)) return rc;
     SIMCHK(s);
-    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a voxel grid of");
-    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
-    if ((s->planes & both) != both)
-        return fail(LCR_ERR_INVALID, "the voxel grid needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the grid): %s",
-                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
     lcr_voxel_grid_spec sp = *spec;
-    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (int rc = planes_ready(s, &sp.cameras, "to make a voxel grid of", "the voxel grid needs", "the grid")) return rc;
     if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
     sp.features |= LCR_VOXEL_OCCUPANCY;
-    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the grid)");
     if (s->voxel_on) {
         // (the boxes compare as float32 values: the kernel then forms the same cells; no corner is a NaN)
         bool same = memcmp(sp.dims, s->voxel_spec.dims, sizeof sp.dims) == 0 && sp.cameras == s->voxel_spec.cameras && sp.ids == s->voxel_spec.ids &&
@@ -2144,12 +2160,9 @@ int lcr_enable_voxel_grid(lcr_sim *s, const lcr_voxel_grid_spec *spec) {
         return fail(LCR_ERR_INVALID, "a voxel grid (%s) is enabled already and fixed for the life of the handle: asked for %s", voxel_spec_text(was, s->voxel_spec), voxel_spec_text(asked, sp));
     }
     LcrVoxel A{};
-    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
-        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
-    };
-    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
-    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
-    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.cam[i] = src[i].cam; A.seg[i] = src[i].seg; A.depth[i] = src[i].depth; A.rgb[i] = src[i].rgb; }
     const size_t N = (size_t)s->dev.n, V = (size_t)sp.dims[0] * sp.dims[1] * sp.dims[2], Cn = (sp.features & LCR_VOXEL_RGB) ? 4 : 1, esize = sp.dtype == LCR_STACK_FLOAT32 ? 4 : 1;
     // guard, voxels, guard (include/lcr.h: LCR_WRIST_GUARD), then source, count, occupied and the camera poses
     Carver C;
@@ -2161,11 +2174,6 @@ int lcr_enable_voxel_grid(lcr_sim *s, const lcr_voxel_grid_spec *spec) {
     const size_t o_cnt = C.take(N * sizeof(int));
     const size_t o_occ = C.take(N * sizeof(int));
     const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
-    const size_t off = C.off;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, off);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the voxel grid failed: %s", off, hipGetErrorString(e));
-    char *base = (char *)mem;
     A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
     A.ids = sp.ids;
     for (int k = 0; k < 3; k++) {
@@ -2176,19 +2184,23 @@ int lcr_enable_voxel_grid(lcr_sim *s, const lcr_voxel_grid_spec *spec) {
     A.channels = (int)Cn; A.f32 = sp.dtype == LCR_STACK_FLOAT32;
     const char *lds = getenv("LCR_VOXEL_LDS");
     A.lds = lds && !strcmp(lds, "big") ? LCR_VOXEL_LDS_BIG : lds && !strcmp(lds, "slab") ? LCR_VOXEL_LDS_SLAB : LCR_VOXEL_LDS_AUTO;
-    A.out = base + o_vox;
-    A.source = sp.source ? (int *)(base + o_src) : nullptr;
-    A.count = (int *)(base + o_cnt);
-    A.occupied = (int *)(base + o_occ);
-    A.pose = (float *)(base + o_pose);
     A.mount = s->wrist.mount;
-    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
-    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
-    s->voxel = A;
-    if (!rc) rc = launch_voxel(s, s->dev, s->stream, nullptr);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->voxel = LcrVoxel{}; return fail(LCR_ERR_UNSUPPORTED, "the voxel-grid kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0], (double)A.inv[1], (double)A.inv[2]); }
-    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { (void)hipFree(mem); s->voxel = LcrVoxel{}; return fail(LCR_ERR_HIP, "making the voxel grid failed: %s", hipGetErrorString((hipError_t)rc)); }
+    void *mem = nullptr;
+    const int rc = bring_up(s, C, guarded, "the voxel grid", &mem,
+        [&](char *base) {
+            A.out = base + o_vox;
+            A.source = sp.source ? (int *)(base + o_src) : nullptr;
+            A.count = (int *)(base + o_cnt);
+            A.occupied = (int *)(base + o_occ);
+            A.pose = (float *)(base + o_pose);
+            s->voxel = A;
+            return launch_voxel(s, s->dev, s->stream, nullptr);
+        },
+        [s] { s->voxel = LcrVoxel{}; });
+    if (rc == LCR_ERR_UNSUPPORTED)
+        return fail(LCR_ERR_UNSUPPORTED, "the voxel-grid kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0],
+                    (double)A.inv[1], (double)A.inv[2]);
+    if (rc) return rc;
     s->voxel_mem = mem;
     s->voxel_spec = sp;
     s->voxel_bytes_per_env = Cn * V * esize;
@@ -2258,16 +2270,10 @@ int lcr_enable_heightmap(lcr_sim *s, const lcr_heightmap_spec *spec) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_heightmap_check(spec)) return rc;
     SIMCHK(s);
-    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to make a heightmap of");
-    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
-    if ((s->planes & both) != both)
-        return fail(LCR_ERR_INVALID, "the heightmap needs both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the map): %s",
-                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
     lcr_heightmap_spec sp = *spec;
-    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
+    if (int rc = planes_ready(s, &sp.cameras, "to make a heightmap of", "the heightmap needs", "the map")) return rc;
     if (sp.ids == 0) sp.ids = LCR_CLOUD_DEFAULT_IDS;
     sp.features |= LCR_HEIGHTMAP_HEIGHT;
-    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the map)");
     if (s->height_on) {
         // (the boxes compare as float32 values: the kernel then forms the same cells; no corner is a NaN)
         bool same = memcmp(sp.dims, s->height_spec.dims, sizeof sp.dims) == 0 && sp.cameras == s->height_spec.cameras && sp.ids == s->height_spec.ids &&
@@ -2278,12 +2284,9 @@ int lcr_enable_heightmap(lcr_sim *s, const lcr_heightmap_spec *spec) {
         return fail(LCR_ERR_INVALID, "a heightmap (%s) is enabled already and fixed for the life of the handle: asked for %s", heightmap_spec_text(was, s->height_spec), heightmap_spec_text(asked, sp));
     }
     LcrHeightmap A{};
-    auto slot = [&A](int cam, const unsigned char *seg, const float *depth, const unsigned char *rgb) {
-        A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.rgb[A.slots] = rgb; A.slots++;
-    };
-    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front, s->dev.img_front);
-    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top, s->dev.img_top);
-    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth, s->wrist.img);
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.cam[i] = src[i].cam; A.seg[i] = src[i].seg; A.depth[i] = src[i].depth; A.rgb[i] = src[i].rgb; }
     const size_t N = (size_t)s->dev.n, M = (size_t)sp.dims[0] * sp.dims[1], Cn = (sp.features & LCR_HEIGHTMAP_RGB) ? 4 : 1;
     // guard, map, guard (include/lcr.h: LCR_WRIST_GUARD), then source, count, filled and the camera poses
     Carver C;
@@ -2295,11 +2298,6 @@ int lcr_enable_heightmap(lcr_sim *s, const lcr_heightmap_spec *spec) {
     const size_t o_cnt = C.take(N * sizeof(int));
     const size_t o_fil = C.take(N * sizeof(int));
     const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
-    const size_t off = C.off;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, off);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the heightmap failed: %s", off, hipGetErrorString(e));
-    char *base = (char *)mem;
     A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
     A.ids = sp.ids;
     for (int k = 0; k < 3; k++) A.lo[k] = sp.lo[k];
@@ -2311,19 +2309,22 @@ int lcr_enable_heightmap(lcr_sim *s, const lcr_heightmap_spec *spec) {
     A.channels = (int)Cn;
     const char *rounds = getenv("LCR_HEIGHTMAP_ROUNDS");
     A.rounds = rounds && !strcmp(rounds, "1") ? 1 : rounds && !strcmp(rounds, "4") ? 4 : 0;
-    A.out = (float *)(base + o_map);
-    A.source = sp.source ? (int *)(base + o_src) : nullptr;
-    A.count = (int *)(base + o_cnt);
-    A.filled = (int *)(base + o_fil);
-    A.pose = (float *)(base + o_pose);
     A.mount = s->wrist.mount;
-    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
-    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
-    s->height = A;
-    if (!rc) rc = launch_heightmap(s, s->dev, s->stream, nullptr);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->height = LcrHeightmap{}; return fail(LCR_ERR_UNSUPPORTED, "the heightmap kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0], (double)A.inv[1]); }
-    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { (void)hipFree(mem); s->height = LcrHeightmap{}; return fail(LCR_ERR_HIP, "making the heightmap failed: %s", hipGetErrorString((hipError_t)rc)); }
+    void *mem = nullptr;
+    const int rc = bring_up(s, C, guarded, "the heightmap", &mem,
+        [&](char *base) {
+            A.out = (float *)(base + o_map);
+            A.source = sp.source ? (int *)(base + o_src) : nullptr;
+            A.count = (int *)(base + o_cnt);
+            A.filled = (int *)(base + o_fil);
+            A.pose = (float *)(base + o_pose);
+            s->height = A;
+            return launch_heightmap(s, s->dev, s->stream, nullptr);
+        },
+        [s] { s->height = LcrHeightmap{}; });
+    if (rc == LCR_ERR_UNSUPPORTED)
+        return fail(LCR_ERR_UNSUPPORTED, "the heightmap kernel is not built for %d cameras at %d x %d with cells of %.9g x %.9g per metre", A.slots, A.W, A.H, (double)A.inv[0], (double)A.inv[1]);
+    if (rc) return rc;
     s->height_mem = mem;
     s->height_spec = sp;
     s->height_bytes_per_env = Cn * M * sizeof(float);
@@ -2397,10 +2398,9 @@ int lcr_enable_object_boxes(lcr_sim *s, const lcr_object_boxes_spec *spec) {
         return fail(LCR_ERR_INVALID, "object boxes (%s) are enabled already and fixed for the life of the handle: asked for %s", boxes_spec_text(was, s->boxes_spec), boxes_spec_text(asked, sp));
     }
     LcrBoxes A{};
-    auto slot = [&A, &sp](const unsigned char *seg, const float *depth) { A.seg[A.slots] = seg; A.depth[A.slots] = sp.depth ? (const unsigned *)depth : nullptr; A.slots++; };
-    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(s->pl.seg_front, s->pl.depth_front);
-    if (sp.cameras & LCR_STACK_CAM_TOP) slot(s->pl.seg_top, s->pl.depth_top);
-    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(s->wrist.seg, s->wrist.depth);
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.seg[i] = src[i].seg; A.depth[i] = sp.depth ? (const unsigned *)src[i].depth : nullptr; }
     A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
     A.n_objects = sp.n_objects;
     for (int o = 0; o < sp.n_objects; o++) A.masks[o] = sp.objects[o];
@@ -2409,16 +2409,11 @@ int lcr_enable_object_boxes(lcr_sim *s, const lcr_object_boxes_spec *spec) {
     C.skip(LCR_WRIST_GUARD);
     const size_t o_out = C.take((size_t)A.n * A.slots * sp.n_objects * 8 * sizeof(int32_t));
     C.skip(LCR_WRIST_GUARD);
-    const size_t off = C.off;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, off);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the object boxes failed: %s", off, hipGetErrorString(e));
-    A.out = (int *)((char *)mem + o_out);
-    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, off, s->stream);
-    if (!rc) rc = lcr_launch_object_boxes(A, s->stream);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); return fail(LCR_ERR_UNSUPPORTED, "the object-boxes kernel is not built for %d cameras at %d x %d with %d objects", A.slots, A.W, A.H, A.n_objects); }
-    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { (void)hipFree(mem); return fail(LCR_ERR_HIP, "making the object boxes failed: %s", hipGetErrorString((hipError_t)rc)); }
+    void *mem = nullptr;   // (all of it guard-filled; nothing is put on the handle before the launch, so there is nothing to take back)
+    const int rc = bring_up(s, C, C.off, "the object boxes", &mem,
+        [&](char *base) { A.out = (int *)(base + o_out); return lcr_launch_object_boxes(A, s->stream); }, [] {});
+    if (rc == LCR_ERR_UNSUPPORTED) return fail(LCR_ERR_UNSUPPORTED, "the object-boxes kernel is not built for %d cameras at %d x %d with %d objects", A.slots, A.W, A.H, A.n_objects);
+    if (rc) return rc;
     s->boxes = A;
     s->boxes_mem = mem;
     s->boxes_spec = sp;
@@ -2455,24 +2450,17 @@ int lcr_enable_normals(lcr_sim *s, const lcr_normals_spec *spec) {
     // the arguments first, the handle afterwards (what can be refused without a device is)
     if (int rc = lcr_normals_check(spec)) return rc;
     SIMCHK(s);
-    if (!s->has_images) return fail(LCR_ERR_INVALID, "sim has no image observations (observation_mode state): there are no frames to give normals to");
-    const uint32_t both = LCR_PLANE_DEPTH | LCR_PLANE_SEGMENTATION;
-    if ((s->planes & both) != both)
-        return fail(LCR_ERR_INVALID, "the surface normals need both image planes, depth and segmentation (lcr_enable_image_planes with planes = 3, before the normals): %s",
-                    s->planes == 0 ? "none is enabled" : (s->planes & LCR_PLANE_DEPTH) ? "the segmentation plane is missing" : "the depth plane is missing");
     lcr_normals_spec sp = *spec;
-    if (sp.cameras == 0) sp.cameras = LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | (s->wrist_on ? LCR_STACK_CAM_WRIST : 0);
-    if ((sp.cameras & LCR_STACK_CAM_WRIST) && !s->wrist_on) return fail(LCR_ERR_INVALID, "cameras selects the wrist camera (4), but the sim has none (lcr_enable_wrist_camera, before the planes and the normals)");
+    if (int rc = planes_ready(s, &sp.cameras, "to give normals to", "the surface normals need", "the normals")) return rc;
     if (s->normals_on) {
         if (sp.cameras == s->normals_spec.cameras && sp.frame == s->normals_spec.frame) return LCR_OK;
         return fail(LCR_ERR_INVALID, "surface normals (cameras %u, frame %d) are enabled already and fixed for the life of the handle: asked for cameras %u, frame %d",
                     s->normals_spec.cameras, s->normals_spec.frame, sp.cameras, sp.frame);
     }
     LcrNormals A{};
-    auto slot = [&A](int cam, const unsigned char *seg, const float *depth) { A.cam[A.slots] = cam; A.seg[A.slots] = seg; A.depth[A.slots] = depth; A.slots++; };
-    if (sp.cameras & LCR_STACK_CAM_FRONT) slot(LCR_CLOUD_CAM_FRONT, s->pl.seg_front, s->pl.depth_front);
-    if (sp.cameras & LCR_STACK_CAM_TOP) slot(LCR_CLOUD_CAM_TOP, s->pl.seg_top, s->pl.depth_top);
-    if (sp.cameras & LCR_STACK_CAM_WRIST) slot(LCR_CLOUD_CAM_WRIST, s->wrist.seg, s->wrist.depth);
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.cam[i] = src[i].cam; A.seg[i] = src[i].seg; A.depth[i] = src[i].depth; }
     const size_t N = (size_t)s->dev.n, plane = N * s->dev.img_w * s->dev.img_h * 4;
     // guard, then per slot the plane and a guard (include/lcr.h: LCR_WRIST_GUARD), then the boxes and the camera poses
     Carver C;
@@ -2482,25 +2470,22 @@ int lcr_enable_normals(lcr_sim *s, const lcr_normals_spec *spec) {
     const size_t guarded = C.off;
     const size_t o_boxes = C.take((size_t)LCR_NORMALS_BOXES * LCR_NORMALS_BOX_FLOATS * N * sizeof(float));
     const size_t o_pose = C.take((size_t)A.slots * 13 * N * sizeof(float));
-    const size_t off = C.off;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, off);
-    if (e != hipSuccess) return fail(LCR_ERR_OOM, "hipMalloc(%zu bytes) for the surface normals failed: %s", off, hipGetErrorString(e));
-    char *base = (char *)mem;
     A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
     A.frame = sp.frame;
     A.ncube = s->dev.task == 4 ? 2 : 1;
-    for (int i = 0; i < A.slots; i++) A.out[i] = (unsigned *)(base + o_plane[i]);
-    A.boxes = (float *)(base + o_boxes);
-    A.pose = (float *)(base + o_pose);
     A.mount = s->wrist.mount;
-    int rc = (int)hipMemsetAsync(mem, LCR_WRIST_GUARD_BYTE, guarded, s->stream);
-    if (!rc) rc = (int)hipMemsetAsync(base + guarded, 0, off - guarded, s->stream);
-    s->normals = A;
-    if (!rc) rc = launch_normals(s, s->dev, s->stream, nullptr);
-    if (rc < 0) { (void)hipStreamSynchronize(s->stream); (void)hipFree(mem); s->normals = LcrNormals{}; return fail(LCR_ERR_UNSUPPORTED, "the normals kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H); }
-    if (!rc) rc = (int)hipStreamSynchronize(s->stream);
-    if (rc) { (void)hipFree(mem); s->normals = LcrNormals{}; return fail(LCR_ERR_HIP, "making the surface normals failed: %s", hipGetErrorString((hipError_t)rc)); }
+    void *mem = nullptr;
+    const int rc = bring_up(s, C, guarded, "the surface normals", &mem,
+        [&](char *base) {
+            for (int i = 0; i < A.slots; i++) A.out[i] = (unsigned *)(base + o_plane[i]);
+            A.boxes = (float *)(base + o_boxes);
+            A.pose = (float *)(base + o_pose);
+            s->normals = A;
+            return launch_normals(s, s->dev, s->stream, nullptr);
+        },
+        [s] { s->normals = LcrNormals{}; });
+    if (rc == LCR_ERR_UNSUPPORTED) return fail(LCR_ERR_UNSUPPORTED, "the normals kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H);
+    if (rc) return rc;
     s->normals_mem = mem;
     s->normals_spec = sp;
     s->normals_on = true;

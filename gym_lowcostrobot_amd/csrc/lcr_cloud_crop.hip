@@ -7,14 +7,15 @@
 //   cameras first   pass 1 needs the poses, so the thread that writes them does so before pass 1 and every thread waits for it -- the device code of the kernels without a
 //                   box, the wrist pose from the link chain included.
 //   pass 1          a group's 16 segmentation bytes are loaded and id-tested as before; a group with at least one candidate by id loads its 16 depth floats (four 16-byte
-//                   loads), forms the point of every pixel by the chain the header pins (crop_point) and tests it against the box (crop_scan).  The count byte is the
+//                   loads), forms the point of every pixel by the chain the header pins (pinned_point) and tests it against the box (crop_scan).  The count byte is the
 //                   number of pixels that pass both.  Four rounds are in flight in the strided kernels (one in the farthest-point kernels, which pay for registers in the
 //                   waves their greedy loop needs): their segmentation loads are issued before any byte is tested, their depth loads before any point is formed.  W is a multiple of 4, not of 16: a group may straddle image rows, so row and px are stepped per pixel from one division a group.
 //   pass 2 / pool   the group and the rank inside it come from the walk as before; the group's ids and depths are loaded again and crop_scan run again, which returns the
 //                   rank-th pixel that passes and ITS point: the point that goes out is the point that was tested.  O(P) (O(Q)) groups: the recomputation is cheap, and
 //                   the LDS footprint stays that of lcr_cloud_lds_bytes.
-// The point is pinned to the bit (include/lcr.h).  This unit is built with the project's flags, -ffast-math among them; every rounded intermediate of crop_point is made
-// opaque to the optimiser, as fps_dist's are, and the fused steps are explicit fmaf calls.  Denormals are kept.
+// The point is pinned to the bit (include/lcr.h).  This unit is built with the project's flags, -ffast-math among them; every rounded intermediate of pinned_point
+// (lcr_cloud_dev.h: the one copy the grid, the map and the normals use too) is made opaque to the optimiser, as fps_dist's are, and the fused steps are explicit fmaf
+// calls.  Denormals are kept.
 // The greedy loop of the farthest-point kernels is the text lcr_cloud_fps.hip runs (lcr_cloud_fps_loop.inc.h).
 #include <hip/hip_runtime.h>
 
@@ -27,30 +28,8 @@ namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));   // 16 B: four depths of a group
 
-// The header's point of pixel (row, px) at depth t through the camera `cam` (ro, X, Y, Z, s as store_cam lays them out), to the bit: hx and hy are exact half-integers
-// (hW = W / 2, hH = H / 2), sx and sy one rounded multiply each, d = fmaf(sx, X, fmaf(sy, Y, - Z)) and p = fmaf(t, d, ro) per axis.  The empty asm statements hide each
-// rounded result from the optimiser: under -ffast-math it may otherwise re-associate or contract across them.
-__device__ __forceinline__ void crop_point(unsigned px, unsigned row, float hW, float hH, float t, const float (&cam)[13], float (&p)[3]) {
-    const float hx = (float)px + 0.5f - hW;
-    const float hy = (float)row + 0.5f - hH;
-    float sx = hx * cam[12];
-    asm("" : "+v"(sx));
-    float sy = -(hy * cam[12]);
-    asm("" : "+v"(sy));
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float i = __builtin_fmaf(sy, cam[6 + k], -cam[9 + k]);
-        asm("" : "+v"(i));
-        float d = __builtin_fmaf(sx, cam[3 + k], i);
-        asm("" : "+v"(d));
-        float q = __builtin_fmaf(t, d, cam[k]);
-        asm("" : "+v"(q));
-        p[k] = q;
-    }
-}
-
 // The 16 pixels of a group that starts at (row, px): w its segmentation bytes, d its depths.  Returns how many are candidates by id AND have their point inside the box
-// (float32 comparisons on the bits crop_point gives).  PICK: the `want`-th of them (from 0) leaves its place in the group in b and its point in p.
+// (float32 comparisons on the bits pinned_point gives, lcr_cloud_dev.h).  PICK: the `want`-th of them (from 0) leaves its place in the group in b and its point in p.
 template <bool PICK>
 __device__ __forceinline__ unsigned crop_scan(const v4u w, const v4f (&d)[4], unsigned ids, unsigned row, unsigned px, unsigned W, float hW, float hH, const float *camsh,
                                               const LcrCloudCrop &BX, unsigned want, unsigned &b, float (&p)[3]) {
@@ -63,7 +42,7 @@ __device__ __forceinline__ unsigned crop_scan(const v4u w, const v4f (&d)[4], un
     for (int k = 0; k < 16; k++) {
         const unsigned hit = is_candidate(ww[k >> 2] >> (8 * (k & 3)), ids);
         float q[3];
-        crop_point(px, row, hW, hH, d[k >> 2][k & 3], cam, q);
+        pinned_point(px, row, hW, hH, d[k >> 2][k & 3], cam, q);
         const bool in = hit && BX.lo[0] <= q[0] && q[0] <= BX.hi[0] && BX.lo[1] <= q[1] && q[1] <= BX.hi[1] && BX.lo[2] <= q[2] && q[2] <= BX.hi[2];
         if constexpr (PICK) {
             if (in && n == want) { b = (unsigned)k; p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; }

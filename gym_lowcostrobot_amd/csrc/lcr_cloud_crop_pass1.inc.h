@@ -1,6 +1,6 @@
 // lcr_cloud_crop_pass1.inc.h -- a statement list, included inside the body of a point-cloud kernel with a crop box (lcr_cloud_crop.hip): lcr_cloud_pass1.inc.h with the
-// cameras BEFORE pass 1 and the inside test in it.  The text is a copy, not a parameter of that list: the kernels without a box stay instruction for instruction what
-// they are (lcr_cloud_dev.h).
+// cameras BEFORE pass 1 and the inside test in it.  Pass 1 and the prefix are a copy of that list's text, not a parameter of it: the kernels without a box stay
+// instruction for instruction what they are (lcr_cloud_dev.h).  The cameras are the one list both include (lcr_obs_cameras.inc.h).
 // In scope before it: `A` (an LcrCloud), `BX` (an LcrCloudCrop: the box), the macro LCR_CLOUD_CROP_ROUNDS (how many rounds of pass 1 are in flight), and the LDS arrays `segpre` [MAX_SEG + 4], `cams` [3][16] and `cnt` (dynamic, lcr_cloud_lds_bytes).
 // It returns from the kernel for a workgroup beyond the last env; behind it, and behind a barrier: tid, lane, wave, env, pixels, gpc, G, nseg, env_px, hW, hH and M are
 // defined, cams, cnt and segpre are filled (segpre[nseg] = M), and the camera poses and count[env] are written.
@@ -15,26 +15,10 @@
     const size_t env_px = (size_t)env * pixels;
     const float hW = 0.5f * (float)A.W, hH = 0.5f * (float)A.H;        // (exact: W, H <= 512)
 
-    // ---- the cameras: one thread, the device code and the arithmetic of lcr_cloud_pass1.inc.h (the pose bits are those of a handle without a box); pass 1 needs them,
-    //      so every thread waits here ----
+    // ---- the cameras: one thread, the statement list lcr_cloud_pass1.inc.h includes (the pose bits are those of a handle without a box); pass 1 needs them, so every
+    //      thread waits here ----
     if (tid == LCR_CLOUD_THREADS - 64) {
-        for (int sl = 0; sl < A.slots; sl++) {
-            LcrCam C;
-            if (A.cam[sl] == LCR_CLOUD_CAM_WRIST) {
-                float q[6];
-                for (int j = 0; j < 6; j++) q[j] = A.qpos[(size_t)j * A.n + env];
-                ArmFrames F;
-                arm_frames(q, F);
-                wrist_camera(F, A.mount, C);
-            } else if (A.var) {
-                C = A.var[A.variant[env]].cam[A.cam[sl]];
-            } else {
-                C = A.cam[sl] == LCR_CLOUD_CAM_FRONT ? A.front : A.top;
-            }
-            store_cam(cams[sl], C);
-            float *po = A.pose + (size_t)sl * 13 * A.n + env;
-            for (int k = 0; k < 13; k++) po[(size_t)k * A.n] = cams[sl][k];
-        }
+#include "lcr_obs_cameras.inc.h"
     }
     __syncthreads();
 

@@ -14,23 +14,7 @@
 
     // ---- the cameras (one thread; the others are on their way through pass 1) ----
     if (tid == LCR_CLOUD_THREADS - 64) {
-        for (int sl = 0; sl < A.slots; sl++) {
-            LcrCam C;
-            if (A.cam[sl] == LCR_CLOUD_CAM_WRIST) {
-                float q[6];
-                for (int j = 0; j < 6; j++) q[j] = A.qpos[(size_t)j * A.n + env];
-                ArmFrames F;
-                arm_frames(q, F);
-                wrist_camera(F, A.mount, C);
-            } else if (A.var) {
-                C = A.var[A.variant[env]].cam[A.cam[sl]];
-            } else {
-                C = A.cam[sl] == LCR_CLOUD_CAM_FRONT ? A.front : A.top;
-            }
-            store_cam(cams[sl], C);
-            float *po = A.pose + (size_t)sl * 13 * A.n + env;
-            for (int k = 0; k < 13; k++) po[(size_t)k * A.n] = cams[sl][k];
-        }
+#include "lcr_obs_cameras.inc.h"
     }
 
     // ---- pass 1: candidates per group, UNROLL rounds in flight; then the totals per segment ----

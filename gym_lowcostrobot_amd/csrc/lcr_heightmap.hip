@@ -1,12 +1,13 @@
 // lcr_heightmap.hip -- the heightmap (lcr_enable_heightmap, include/lcr.h): one kernel that turns the selected cameras' segmentation, depth and colour planes into an
 // orthographic top-down map per env -- the height of the highest surface above every cell of a fixed box of the world frame and, with rgb, its colour -- behind the frame
-// kernels on their stream.  A unit of its own: the cloud's and the grid's kernels stay what they are, and a handle without a map launches nothing of this file.
+// kernels on their stream.  A unit of its own: a handle without a map launches nothing of this file.  What it has in common with the cloud's and the grid's kernels is in
+// lcr_cloud_dev.h, once.
 //
 // The mapping is the voxel grid's (a workgroup of four waves is ONE env; any n works, no workgroup spans envs):
-//   cameras   the thread that writes the poses does so first and every thread waits for it: the device code of the cloud kernels, the wrist pose from the link chain included.
+//   cameras   the thread that writes the poses does so first and every thread waits for it: the statement list of the cloud kernels (lcr_obs_cameras.inc.h), the wrist pose from the link chain included.
 //   scan      thread t of round r takes the 16-pixel GROUP g = 256 r + t of the env's slots x H W / 16 groups (camera slot major).  Its 16 segmentation bytes are one 16-byte
 //             load; a group with at least one candidate by id loads its 16 depth floats (four 16-byte loads), forms the point of every pixel by the chain the header pins
-//             (height_point: a copy of voxel_point's text), the cell of the point along x and y (height_axis: voxel_axis's text) and the height word along z.  One or four
+//             (pinned_point), the cell of the point along x and y (cell_axis) and the height word along z (height_word).  One or four
 //             rounds are in flight (ROUNDS): their segmentation loads are issued before any byte is tested, their depth loads before any point is formed.  A candidate inside
 //             the box takes ONE atomicMax of its 64-bit key -- height word high, 0xFFFFFFFF - global pixel index low -- on its cell's key in LDS, a single ds_max_u64: an
 //             order-independent maximum, so the map does not depend on the order lanes arrive in -- and is counted.
@@ -15,14 +16,14 @@
 // LDS: one 8-byte key a cell.  Up to 8 192 cells are at most 64 KiB of dynamic LDS and one pass.  A larger map is made in the fewest passes over the planes, equal slabs of
 // WHOLE ROWS of y of at most 8 192 cells each; the bytes are the same for any slab count.
 // The point, the cell and the height are pinned to the bit (include/lcr.h).  This unit is built with the project's flags, -ffast-math among them; every rounded intermediate
-// is made opaque to the optimiser, as voxel_point's are, and the fused steps are explicit fmaf calls.  Denormals are kept.
+// is made opaque to the optimiser (pinned_point, cell_axis: lcr_cloud_dev.h; height_word), and the fused steps are explicit fmaf calls.  Denormals are kept.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/lcr.h"
 #include "lcr_heightmap.h"
-#include "lcr_cloud_dev.h"   // is_candidate, count_word, store_cam and the wrist pose: shared with the cloud kernels
+#include "lcr_cloud_dev.h"   // is_candidate, count_word, store_cam, pinned_point, cell_axis, elem, wave_sum and the wrist pose: shared with the cloud kernels and the grid
 
 namespace {
 
@@ -31,38 +32,6 @@ typedef unsigned long long u64;
 
 constexpr unsigned ALL = 0xFFFFFFFFu;   // a key's low word is ALL - g: never 0, since g < 2^32 - 1
 
-// The header's point of pixel (row, px) at depth t through the camera `cam` (ro, X, Y, Z, s as store_cam lays them out), to the bit: voxel_point of lcr_voxel.hip, as a
-// copy of its text (that unit stays instruction for instruction what it is).  The empty asm statements hide each rounded result from the optimiser
-__device__ __forceinline__ void height_point(unsigned px, unsigned row, float hW, float hH, float t, const float (&cam)[13], float (&p)[3]) {
-    const float hx = (float)px + 0.5f - hW;
-    const float hy = (float)row + 0.5f - hH;
-    float sx = hx * cam[12];
-    asm("" : "+v"(sx));
-    float sy = -(hy * cam[12]);
-    asm("" : "+v"(sy));
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float i = __builtin_fmaf(sy, cam[6 + k], -cam[9 + k]);
-        asm("" : "+v"(i));
-        float d = __builtin_fmaf(sx, cam[3 + k], i);
-        asm("" : "+v"(d));
-        float q = __builtin_fmaf(t, d, cam[k]);
-        asm("" : "+v"(q));
-        p[k] = q;
-    }
-}
-
-// The header's cell of a point along x or y: u = p - lo, one float32 subtraction; v = u inv, one rounded float32 multiply; inside iff u >= 0 && v < H; the index is
-// (int)v.  Both operations are opaque to the optimiser
-__device__ __forceinline__ bool height_axis(float p, float lo, float inv, float D, unsigned &i) {
-    float u = p - lo;
-    asm("" : "+v"(u));
-    float v = u * inv;
-    asm("" : "+v"(v));
-    i = (unsigned)(int)v;
-    return u >= 0.0f && v < D;
-}
-
 // The header's height of a point: u = p - lo, one opaque float32 subtraction; inside iff u >= 0 && p <= hi (both faces belong to the box); the height word is the bit
 // pattern of u with the sign bit cleared (u = - 0.0 passes the test and is the height + 0.0), which orders as the heights do
 __device__ __forceinline__ bool height_word(float p, float lo, float hi, unsigned &hb) {
@@ -70,15 +39,6 @@ __device__ __forceinline__ bool height_word(float p, float lo, float hi, unsigne
     asm("" : "+v"(u));
     hb = __float_as_uint(u) & 0x7fffffffu;
     return u >= 0.0f && p <= hi;
-}
-
-// the stack's float32 element: one correctly rounded multiply by the float32 constant 1 / 255
-__device__ __forceinline__ float elem(unsigned x) { return (float)x * (1.0f / 255.0f); }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // ROUNDS: the rounds of the scan in flight, as the grid's kernel has them: four hold 16 depth registers each, one keeps the kernel small enough for five workgroups a CU
@@ -102,26 +62,10 @@ __global__ __launch_bounds__(LCR_HEIGHTMAP_THREADS) void lcr_heightmap_kernel(co
     const size_t M = (size_t)Hx * Hy;
     const float fHx = (float)A.D[0], fHy = (float)A.D[1];
 
-    // ---- the cameras: one thread, the device code and the arithmetic of the cloud kernels (the pose bits are the cloud's); the scan needs them, so every thread waits ----
+    // ---- the cameras: one thread, the statement list of the cloud kernels (the pose bits are the cloud's); the scan needs them, so every thread waits ----
     if (tid == 0) tot[0] = tot[1] = 0u;
     if (tid == LCR_HEIGHTMAP_THREADS - 64) {
-        for (int sl = 0; sl < A.slots; sl++) {
-            LcrCam C;
-            if (A.cam[sl] == LCR_CLOUD_CAM_WRIST) {
-                float q[6];
-                for (int j = 0; j < 6; j++) q[j] = A.qpos[(size_t)j * A.n + env];
-                ArmFrames F;
-                arm_frames(q, F);
-                wrist_camera(F, A.mount, C);
-            } else if (A.var) {
-                C = A.var[A.variant[env]].cam[A.cam[sl]];
-            } else {
-                C = A.cam[sl] == LCR_CLOUD_CAM_FRONT ? A.front : A.top;
-            }
-            store_cam(cams[sl], C);
-            float *po = A.pose + (size_t)sl * 13 * A.n + env;
-            for (int k = 0; k < 13; k++) po[(size_t)k * A.n] = cams[sl][k];
-        }
+#include "lcr_obs_cameras.inc.h"
     }
     __syncthreads();
 
@@ -178,10 +122,10 @@ __global__ __launch_bounds__(LCR_HEIGHTMAP_THREADS) void lcr_heightmap_kernel(co
                 for (int k = 0; k < 16; k++) {
                     const unsigned hit = is_candidate(ww[k >> 2] >> (8 * (k & 3)), A.ids);
                     float p[3];
-                    height_point(px, row, hW, hH, d[u][k >> 2][k & 3], cam, p);
+                    pinned_point(px, row, hW, hH, d[u][k >> 2][k & 3], cam, p);
                     unsigned ix, iy, hb;
-                    const bool inx = height_axis(p[0], A.lo[0], A.inv[0], fHx, ix);
-                    const bool iny = height_axis(p[1], A.lo[1], A.inv[1], fHy, iy);
+                    const bool inx = cell_axis(p[0], A.lo[0], A.inv[0], fHx, ix);
+                    const bool iny = cell_axis(p[1], A.lo[1], A.inv[1], fHy, iy);
                     const bool inz = height_word(p[2], A.lo[2], A.hi_z, hb);
                     const unsigned ly = iy - y0;                       // (wraps below the slab: then >= ny)
                     const unsigned idx = ly * Hx + ix;

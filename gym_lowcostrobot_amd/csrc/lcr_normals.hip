@@ -12,19 +12,19 @@
 //             row.  Four trips are in flight: their segmentation loads are issued before any byte is tested, their depth loads before any point is formed.  (The other
 //             mapping that was tried, a lane owning a 16-pixel chunk as in lcr_boxes.hip, took 1.6 times as long at 240 x 320: profiles/surface_normals.txt has both.)
 //             A lane whose bytes are all sky or floor -- most of a frame -- answers from the table without loading depth; only lanes with a box pixel load the depth words
-//             and run the chain of the header: the pinned point (normal_point: a copy of voxel_point's text), u = p - c, the three box coordinates, e = |l| - h, the
+//             and run the chain of the header: the pinned point (pinned_point, lcr_cloud_dev.h), u = p - c, the three box coordinates, e = |l| - h, the
 //             largest e.  The box is read from LDS at a per-lane index (box stride 17 dwords: the nine boxes lie in different banks).
 //   output    one dword a pixel, 16-byte stores.
 // Nothing depends on the order lanes arrive in and there are no atomics: every output word is a function of its own pixel and the set-up.
 // The rule is pinned to the bit (include/lcr.h).  This unit is built with the project's flags, -ffast-math among them; every rounded intermediate is made opaque to the
-// optimiser, as voxel_point's are, and the fused steps are explicit fmaf calls.
+// optimiser (pinned_point; pinned_dot, quantise), and the fused steps are explicit fmaf calls.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/lcr.h"
 #include "lcr_normals.h"
-#include "lcr_cloud_dev.h"      // store_cam and the wrist pose: shared with the cloud kernels
+#include "lcr_cloud_dev.h"      // store_cam, pinned_point and the wrist pose: shared with the cloud kernels, the grid and the map
 #include "lcr_opaque_boxes.h"
 
 namespace {
@@ -34,27 +34,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));   // 16 B: four depths
 constexpr int BS = 17;                                    // dwords of a box in LDS: 15 used, an odd stride
 constexpr int TAB = 2 + 6 * LCR_NORMALS_BOXES;            // sky, floor, six faces a box
 constexpr unsigned SETUP = LCR_NORMALS_THREADS - 64;      // the first lane of the last wave
-
-// The header's point of pixel (row, px) at depth t through the camera `cam` (ro, X, Y, Z, s as store_cam lays them out), to the bit: voxel_point of lcr_voxel.hip, as a copy
-// of its text (that unit stays instruction for instruction what it is).  The empty asm statements hide each rounded result from the optimiser
-__device__ __forceinline__ void normal_point(unsigned px, unsigned row, float hW, float hH, float t, const float (&cam)[13], float (&p)[3]) {
-    const float hx = (float)px + 0.5f - hW;
-    const float hy = (float)row + 0.5f - hH;
-    float sx = hx * cam[12];
-    asm("" : "+v"(sx));
-    float sy = -(hy * cam[12]);
-    asm("" : "+v"(sy));
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float i = __builtin_fmaf(sy, cam[6 + k], -cam[9 + k]);
-        asm("" : "+v"(i));
-        float d = __builtin_fmaf(sx, cam[3 + k], i);
-        asm("" : "+v"(d));
-        float q = __builtin_fmaf(t, d, cam[k]);
-        asm("" : "+v"(q));
-        p[k] = q;
-    }
-}
 
 // lcr_arm.h's dot, fmaf(a.x, b.x, fmaf(a.y, b.y, a.z b.z)), with every rounded step opaque
 __device__ __forceinline__ float pinned_dot(float ax, float ay, float az, float bx, float by, float bz) {
@@ -78,7 +57,7 @@ __device__ __forceinline__ unsigned quantise(float c) {
 // the table index of box pixel (row, px) with surface id `id` (2 .. 10) at depth t: 2 + 6 box + 2 axis + side.  `box`: the nine boxes in LDS
 __device__ __forceinline__ unsigned face_of(unsigned id, unsigned px, unsigned row, float hW, float hH, float t, const float (&cam)[13], const float *box) {
     float p[3];
-    normal_point(px, row, hW, hH, t, cam, p);
+    pinned_point(px, row, hW, hH, t, cam, p);
     const unsigned b = id - 2u;
     const float *B = box + b * BS;
     float u[3];
@@ -117,7 +96,8 @@ __global__ __launch_bounds__(LCR_NORMALS_THREADS) void lcr_normals_kernel(const 
     const unsigned quads = pixels >> 2;   // (W is a multiple of 4: a quad lies in one row)
     const float hW = 0.5f * (float)A.W, hH = 0.5f * (float)A.H;   // (exact: W, H <= 512)
 
-    // ---- set-up: the camera and the boxes by one lane, the table by its wave ----
+    // ---- set-up: the camera and the boxes by one lane, the table by its wave.  The camera is the ONE-SLOT form of the shared list lcr_obs_cameras.inc.h (a workgroup here
+    //      is one slot, and A.cam[] is read through a select chain): the same arithmetic and the same pose bits, kept as its own text ----
     if (tid == SETUP) {
         const int which = slot == 0 ? A.cam[0] : slot == 1 ? A.cam[1] : A.cam[2];
         LcrCam C;

@@ -1,7 +1,7 @@
 // lcr_opaque_boxes.h -- where the nine OPAQUE boxes of an env stand: the seven arm boxes (base_link, link_1 .. link_6), the cube and the second cube (StackTwoCubes), in the
 // order of the surface ids 2 .. 10 of the segmentation plane.  Device code for the kernels that need the boxes behind the frame kernels (lcr_normals.hip).
-// It is build_scene's placement of lcr_render.hip as a COPY of its text -- base_box, arm_frames + local_point with the lcrm::ARMB* constants, quat_to_cols --, as voxel_point
-// is a copy of crop_point: lcr_render.hip stays instruction for instruction what it is.  Colours, the translucent marker and the per-camera constants are not in it.
+// It is build_scene's placement of lcr_render.hip as a COPY of its text -- base_box, arm_frames + local_point with the lcrm::ARMB* constants, quat_to_cols --: the render
+// kernels are not touched, so lcr_render.hip stays instruction for instruction what it is.  Colours, the translucent marker and the per-camera constants are not in it.
 #pragma once
 #include "lcr_arm.h"
 

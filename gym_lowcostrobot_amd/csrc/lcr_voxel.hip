@@ -1,12 +1,12 @@
 // lcr_voxel.hip -- the voxel grid (lcr_enable_voxel_grid, include/lcr.h): one kernel that turns the selected cameras' segmentation, depth and colour planes into a dense
-// occupancy (and colour) grid over a fixed box of the world frame per env, behind the frame kernels on their stream.  A unit of its own: the cloud's kernels stay what they
-// are, and a handle without a grid launches nothing of this file.
+// occupancy (and colour) grid over a fixed box of the world frame per env, behind the frame kernels on their stream.  A unit of its own: a handle without a grid launches
+// nothing of this file.  What it has in common with the cloud's kernels is in lcr_cloud_dev.h, once.
 //
 // The mapping is the cloud's (a workgroup of four waves is ONE env; any n works, no workgroup spans envs):
-//   cameras   the thread that writes the poses does so first and every thread waits for it: the device code of the cloud kernels, the wrist pose from the link chain included.
+//   cameras   the thread that writes the poses does so first and every thread waits for it: the statement list of the cloud kernels (lcr_obs_cameras.inc.h), the wrist pose from the link chain included.
 //   scan      thread t of round r takes the 16-pixel GROUP g = 256 r + t of the env's slots x H W / 16 groups (camera slot major).  Its 16 segmentation bytes are one 16-byte
 //             load; a group with at least one candidate by id loads its 16 depth floats (four 16-byte loads), forms the point of every pixel by the chain the header pins
-//             (voxel_point: a copy of crop_point's text) and the voxel of the point (voxel_axis).  One or four rounds are in flight (ROUNDS): their segmentation loads are issued before any
+//             (pinned_point) and the voxel of the point (cell_axis).  One or four rounds are in flight (ROUNDS): their segmentation loads are issued before any
 //             byte is tested, their depth loads before any point is formed.  A candidate inside the grid takes atomicMin(global pixel index) on its voxel's word in LDS --
 //             an order-independent minimum: the grid does not depend on the order lanes arrive in -- and is counted.
 //   output    behind a barrier each thread takes four voxels along x: one 16-byte LDS read; a dword of uint8 occupancy or 16 B of float32; the colour bytes gathered through
@@ -14,61 +14,20 @@
 // LDS: one word a voxel.  V <= 16 384 is at most 64 KiB of dynamic LDS.  A larger grid is made in passes over the planes, one z-slab of at most 16 384 voxels each (the
 // default), or held whole in a build with 128 KiB of static LDS, one workgroup a CU (LCR_VOXEL_LDS=slab|big; the A/B is in profiles/voxel_grid.txt).
 // The point and the voxel are pinned to the bit (include/lcr.h).  This unit is built with the project's flags, -ffast-math among them; every rounded intermediate is made
-// opaque to the optimiser, as crop_point's are, and the fused steps are explicit fmaf calls.  Denormals are kept.
+// opaque to the optimiser (pinned_point, cell_axis: lcr_cloud_dev.h), and the fused steps are explicit fmaf calls.  Denormals are kept.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/lcr.h"
 #include "lcr_voxel.h"
-#include "lcr_cloud_dev.h"   // is_candidate, count_word, store_cam and the wrist pose: shared with the cloud kernels
+#include "lcr_cloud_dev.h"   // is_candidate, count_word, store_cam, pinned_point, cell_axis, elem, wave_sum and the wrist pose: shared with the cloud kernels and the map
 
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));   // 16 B: four depths of a group, four float32 elements of the grid
 
 constexpr unsigned EMPTY = 0xFFFFFFFFu;
-
-// The header's point of pixel (row, px) at depth t through the camera `cam` (ro, X, Y, Z, s as store_cam lays them out), to the bit: crop_point of lcr_cloud_crop.hip, as a
-// copy of its text (that unit stays instruction for instruction what it is).  The empty asm statements hide each rounded result from the optimiser
-__device__ __forceinline__ void voxel_point(unsigned px, unsigned row, float hW, float hH, float t, const float (&cam)[13], float (&p)[3]) {
-    const float hx = (float)px + 0.5f - hW;
-    const float hy = (float)row + 0.5f - hH;
-    float sx = hx * cam[12];
-    asm("" : "+v"(sx));
-    float sy = -(hy * cam[12]);
-    asm("" : "+v"(sy));
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float i = __builtin_fmaf(sy, cam[6 + k], -cam[9 + k]);
-        asm("" : "+v"(i));
-        float d = __builtin_fmaf(sx, cam[3 + k], i);
-        asm("" : "+v"(d));
-        float q = __builtin_fmaf(t, d, cam[k]);
-        asm("" : "+v"(q));
-        p[k] = q;
-    }
-}
-
-// The header's voxel of a point along one axis: u = p - lo, one float32 subtraction; v = u inv, one rounded float32 multiply; inside iff u >= 0 && v < D; the index is
-// (int)v.  Both operations are opaque to the optimiser
-__device__ __forceinline__ bool voxel_axis(float p, float lo, float inv, float D, unsigned &i) {
-    float u = p - lo;
-    asm("" : "+v"(u));
-    float v = u * inv;
-    asm("" : "+v"(v));
-    i = (unsigned)(int)v;
-    return u >= 0.0f && v < D;
-}
-
-// the stack's float32 element: one correctly rounded multiply by the float32 constant 1 / 255
-__device__ __forceinline__ float elem(unsigned x) { return (float)x * (1.0f / 255.0f); }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // ROUNDS: the rounds of the scan in flight.  Four hold 16 depth registers each (185 VGPRs: two workgroups a CU), one keeps the kernel at 81 (five): four where the grid's words
 // leave room for two workgroups anyway, one where they leave room for more (lcr_launch_voxel_grid; the A/B is in profiles/voxel_grid.txt)
@@ -93,26 +52,10 @@ __global__ __launch_bounds__(LCR_VOXEL_THREADS) void lcr_voxel_grid_kernel(const
     const size_t V = (size_t)DxDy * Dz;
     const float fDx = (float)A.D[0], fDy = (float)A.D[1], fDz = (float)A.D[2];
 
-    // ---- the cameras: one thread, the device code and the arithmetic of the cloud kernels (the pose bits are the cloud's); the scan needs them, so every thread waits ----
+    // ---- the cameras: one thread, the statement list of the cloud kernels (the pose bits are the cloud's); the scan needs them, so every thread waits ----
     if (tid == 0) tot[0] = tot[1] = 0u;
     if (tid == LCR_VOXEL_THREADS - 64) {
-        for (int sl = 0; sl < A.slots; sl++) {
-            LcrCam C;
-            if (A.cam[sl] == LCR_CLOUD_CAM_WRIST) {
-                float q[6];
-                for (int j = 0; j < 6; j++) q[j] = A.qpos[(size_t)j * A.n + env];
-                ArmFrames F;
-                arm_frames(q, F);
-                wrist_camera(F, A.mount, C);
-            } else if (A.var) {
-                C = A.var[A.variant[env]].cam[A.cam[sl]];
-            } else {
-                C = A.cam[sl] == LCR_CLOUD_CAM_FRONT ? A.front : A.top;
-            }
-            store_cam(cams[sl], C);
-            float *po = A.pose + (size_t)sl * 13 * A.n + env;
-            for (int k = 0; k < 13; k++) po[(size_t)k * A.n] = cams[sl][k];
-        }
+#include "lcr_obs_cameras.inc.h"
     }
     __syncthreads();
 
@@ -169,11 +112,11 @@ __global__ __launch_bounds__(LCR_VOXEL_THREADS) void lcr_voxel_grid_kernel(const
                 for (int k = 0; k < 16; k++) {
                     const unsigned hit = is_candidate(ww[k >> 2] >> (8 * (k & 3)), A.ids);
                     float p[3];
-                    voxel_point(px, row, hW, hH, d[u][k >> 2][k & 3], cam, p);
+                    pinned_point(px, row, hW, hH, d[u][k >> 2][k & 3], cam, p);
                     unsigned ix, iy, iz;
-                    const bool inx = voxel_axis(p[0], A.lo[0], A.inv[0], fDx, ix);
-                    const bool iny = voxel_axis(p[1], A.lo[1], A.inv[1], fDy, iy);
-                    const bool inz = voxel_axis(p[2], A.lo[2], A.inv[2], fDz, iz);
+                    const bool inx = cell_axis(p[0], A.lo[0], A.inv[0], fDx, ix);
+                    const bool iny = cell_axis(p[1], A.lo[1], A.inv[1], fDy, iy);
+                    const bool inz = cell_axis(p[2], A.lo[2], A.inv[2], fDz, iz);
                     const unsigned lz = iz - z0;                       // (wraps below the slab: then >= nz)
                     const unsigned idx = lz * DxDy + iy * Dx + ix;
                     // (idx < words follows from the three tests; the integer test keeps the LDS address inside the pass whatever a float compare makes of a NaN)
