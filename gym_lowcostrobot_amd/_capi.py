@@ -80,6 +80,7 @@ SYMBOLS = [
     "lcr_heightmap_check", "lcr_enable_heightmap", "lcr_get_heightmap",
     "lcr_object_boxes_check", "lcr_enable_object_boxes", "lcr_get_object_boxes",
     "lcr_normals_check", "lcr_enable_normals", "lcr_get_normals",
+    "lcr_motion_check", "lcr_enable_motion_vectors", "lcr_get_motion_vectors",
     "lcr_enable_obs_stack_planes", "lcr_get_obs_stack_planes",
 ]
 
@@ -914,6 +915,56 @@ class LcrNormalsView(ctypes.Structure):
     ]
 
 
+class MotionSpec(ctypes.Structure):
+    """lcr_motion_spec: the cameras of the motion vectors (include/lcr.h)"""
+    _fields_ = [
+        ("cameras", ctypes.c_uint32),   # STACK_CAMERAS bits; 0 = every camera the handle has
+    ]
+
+    def as_dict(self):
+        """cameras as names"""
+        return {"cameras": tuple(n for n, b in STACK_CAMERAS.items() if self.cameras & b)}
+
+    @classmethod
+    def from_any(cls, v, wrist=False):
+        """a MotionSpec, True (the defaults), or a dict with cameras.  `wrist`: the handle has a wrist camera (the default cameras are every camera the handle has)"""
+        if isinstance(v, cls):
+            return v
+        if v is True:
+            v = {}
+        if not isinstance(v, dict):
+            raise ValueError(f"motion_vectors must be None, True or a dict of cameras, got {v!r}")
+        v = dict(v)
+        out = cls()
+        cams = v.pop("cameras", None)
+        if cams is None:
+            out.cameras = STACK_CAMERAS["front"] | STACK_CAMERAS["top"] | (STACK_CAMERAS["wrist"] if wrist else 0)
+        else:
+            if isinstance(cams, str) or not hasattr(cams, "__iter__") or not all(isinstance(c, str) and c in STACK_CAMERAS for c in cams) or len(cams) == 0:
+                raise ValueError(f"motion_vectors: cameras must be a non-empty tuple drawn from 'front', 'top' and 'wrist', got {cams!r}")
+            out.cameras = sum(STACK_CAMERAS[c] for c in set(cams))
+        if v:
+            raise ValueError(f"unknown motion_vectors fields {sorted(v)}")
+        return out
+
+
+class LcrMotionView(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_int32),
+        ("spec", MotionSpec),                   # as enabled, cameras resolved
+        ("slots", ctypes.c_int32),
+        ("image_width", ctypes.c_int32),
+        ("image_height", ctypes.c_int32),
+        ("flow_front", ctypes.c_void_p),        # [N][H][W][2] float16, or NULL
+        ("flow_top", ctypes.c_void_p),
+        ("flow_wrist", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),             # [N] uint8
+        ("boxes", ctypes.c_void_p),             # [2][9][15][N] float32: now, before
+        ("camera_pose", ctypes.c_void_p),       # [2][slots][13][N] float32: now, before
+        ("bytes_per_env", ctypes.c_uint64),
+    ]
+
+
 class LcrOutView(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int32),
@@ -1066,6 +1117,9 @@ def load():
     L.lcr_normals_check.argtypes = [ctypes.POINTER(NormalsSpec)]
     L.lcr_enable_normals.argtypes = [vp, ctypes.POINTER(NormalsSpec)]
     L.lcr_get_normals.argtypes = [vp, ctypes.POINTER(LcrNormalsView)]
+    L.lcr_motion_check.argtypes = [ctypes.POINTER(MotionSpec)]
+    L.lcr_enable_motion_vectors.argtypes = [vp, ctypes.POINTER(MotionSpec)]
+    L.lcr_get_motion_vectors.argtypes = [vp, ctypes.POINTER(LcrMotionView)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("lcr_last_error", "lcr_destroy"):

@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblcr_hip.so")
-SOURCES = ["lcr_capi.hip", "lcr_kernels.hip", "lcr_kernels2.hip", "lcr_render.hip", "lcr_stack.hip", "lcr_cloud.hip", "lcr_cloud_fps.hip", "lcr_cloud_crop.hip", "lcr_voxel.hip", "lcr_heightmap.hip", "lcr_boxes.hip", "lcr_normals.hip"]   # (bench.kernel_sha16 and the tools hash / compile these)
-HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_obs_cameras.inc.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_normals.h", "lcr_opaque_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
+SOURCES = ["lcr_capi.hip", "lcr_kernels.hip", "lcr_kernels2.hip", "lcr_render.hip", "lcr_stack.hip", "lcr_cloud.hip", "lcr_cloud_fps.hip", "lcr_cloud_crop.hip", "lcr_voxel.hip", "lcr_heightmap.hip", "lcr_boxes.hip", "lcr_normals.hip", "lcr_flow.hip"]   # (bench.kernel_sha16 and the tools hash / compile these)
+HEADERS = ["lcr_device.h", "lcr_arm.h", "lcr_model_gen.h", "lcr_step_common.h", "lcr_newton.h", "lcr_newton_coop.h", "lcr_stack.h", "lcr_cloud.h", "lcr_cloud_dev.h", "lcr_obs_cameras.inc.h", "lcr_cloud_pass1.inc.h", "lcr_cloud_point.inc.h", "lcr_cloud_fps_dev.h", "lcr_cloud_fps_loop.inc.h", "lcr_cloud_crop_pass1.inc.h", "lcr_cloud_crop_point.inc.h", "lcr_voxel.h", "lcr_heightmap.h", "lcr_boxes.h", "lcr_normals.h", "lcr_flow.h", "lcr_opaque_boxes.h", "lcr_wrist_pose.h", os.path.join("..", "..", "include", "lcr.h")]
 # -ffast-math: the kernels carry no NaN/inf/signed-zero semantics (the -0.0 sparse reward is built from its bit pattern,
 # the fp64 reset sampling uses explicitly rounded __dmul_rn/__dadd_rn); -fno-slp-vectorize: packed-f32 formation by the
 # SLP vectoriser costs more moves than it saves here (measured on MI355X: 0.340 ms -> 0.286 ms per 65 536-env step).
@@ -63,6 +63,10 @@ UNITS = [("lcr_capi.hip", "lcr_capi.o", []),
          # the surface normals (lcr_enable_normals): one kernel; a unit of its own.  The project's flags: the point, the box coordinates and the quantisation
          # its header pins to the bit are kept from -ffast-math inside the source (pinned_point, lcr_cloud_dev.h; pinned_dot, quantise)
          ("lcr_normals.hip", "lcr_normals.o", []),
+         # the motion vectors (lcr_enable_motion_vectors): one kernel; a unit of its own, and the one unit NOT built with -ffast-math.  Its header pins gx = a / den as one
+         # correctly rounded float32 division, and under -ffast-math every spelling of it (/, __fdiv_rn, #pragma clang fp reciprocal(off), float_control) compiles to
+         # v_rcp_f32 and a multiply on gfx950; with the two flags appended it is the IEEE sequence v_div_scale / v_div_fmas / v_div_fixup, and nothing is contracted
+         ("lcr_flow.hip", "lcr_flow.o", ["-fno-fast-math", "-ffp-contract=off"]),
          ("lcr_kernels.hip", "lcr_kernels.o", ["-DLCR_PART=0"]), ("lcr_kernels.hip", "lcr_kernels_loop.o", ["-DLCR_PART=6"]),
          ("lcr_kernels.hip", "lcr_kernels_loop_newton.o", ["-DLCR_PART=7"] + ITER_ILP),   # (PushCubeLoop's Newton kernels: 6.60 -> 5.98 ms with it, its sweep kernels 0.652 -> 0.730: two units)
          ("lcr_kernels.hip", "lcr_kernels_stack.o", ["-DLCR_PART=2"]), ("lcr_kernels.hip", "lcr_kernels_stack_big.o", ["-DLCR_PART=3"]),

@@ -19,6 +19,7 @@
 #include "lcr_heightmap.h"
 #include "lcr_boxes.h"
 #include "lcr_normals.h"
+#include "lcr_flow.h"
 
 static_assert(LCR_NWARM == LCR_DEV_NWARM, "include/lcr.h and lcr_device.h disagree on the carried-force block");
 
@@ -219,6 +220,13 @@ struct lcr_sim {
     lcr_normals_spec normals_spec;     // as enabled, cameras resolved
     LcrNormals normals;                // the arguments of their kernel (the cameras and the pose snapshot are set per launch)
     void *normals_mem;
+    // the motion vectors (lcr_enable_motion_vectors): one allocation -- guard, then per slot plane and guard, boxes, camera poses (now and before each), valid, the two
+    // snapshots of did_reset a handle without a stack has nowhere else --, fixed for the life of the handle
+    bool flow_on;
+    lcr_motion_spec flow_spec;         // as enabled, cameras resolved
+    LcrFlow flow;                      // the arguments of their kernel (the cameras, the pose snapshot, the flags and the mode are set per launch)
+    void *flow_mem;
+    unsigned char *flow_reset[2];      // beside snap_qpos / snap_target / snap_look; used when there is no stack (whose snap_reset serves both)
 };
 
 // the looks P's envs are drawn with: the current ones, or `look` ([10][P.n]: a snapshot, the gathered terminal looks)
@@ -285,10 +293,26 @@ static int launch_voxel(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
 static int launch_heightmap(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) { return lcr_launch_heightmap(with_cameras(s, P, look, s->height), stream); }
 static int launch_normals(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look) { return lcr_launch_normals(with_cameras(s, P, look, s->normals), stream); }
 
+// the motion-vector kernel, the last behind the frame kernels on their stream.  `step`: the launch of lcr_step, the only one that measures -- "now" (the boxes and the
+// poses of the previous launch) first becomes "before", on the same stream, so the kernel reads only "before" and writes only "now"; `flags` is did_reset of that step.
+// Every other launch restarts every env: zero planes, valid 0, "before" a copy of "now"
+static int launch_flow(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *flags, bool step) {
+    LcrFlow A = with_cameras(s, P, look, s->flow);
+    A.restart = step ? 0 : 1;
+    A.flags = step ? flags : nullptr;
+    if (step) {
+        const size_t N = (size_t)A.n, boxes = (size_t)LCR_FLOW_BOXES * LCR_FLOW_BOX_FLOATS * N, poses = (size_t)A.slots * 13 * N;
+        hipError_t e = hipMemcpyAsync(A.boxes + boxes, A.boxes, boxes * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(A.pose + poses, A.pose, poses * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    return lcr_launch_flow(A, stream);
+}
+
 // frames, then stack, then cloud: what every entry point that has changed the poses or the looks enqueues on `stream` -- the frames of P's envs (`look` as in look_args) and, on a
 // handle with a stack, the stack kernel behind them (`reset_flags`, `op` as in launch_stack), on a handle with a point cloud its kernel, on one with a voxel grid its kernel, on
 // one with a heightmap its kernel, on one with object boxes their kernel (it reads the planes alone: no camera, no look, no pose), and on one with surface normals their
-// kernel last
+// kernel, and on one with motion vectors their kernel last (a step measures, every other caller restarts: launch_flow)
 static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const int *look, const unsigned char *reset_flags, int op, bool step = false) {
     LAUNCHCHK("render", launch_frames(s, P, stream, look));
     if (s->stack_on) LAUNCHCHK("stack kernel", launch_stack(s, stream, reset_flags, op, step));
@@ -297,6 +321,7 @@ static int frames_after(lcr_sim *s, const LcrDev &P, hipStream_t stream, const i
     if (s->height_on) LAUNCHCHK("heightmap kernel", launch_heightmap(s, P, stream, look));
     if (s->boxes_on) LAUNCHCHK("object-boxes kernel", lcr_launch_object_boxes(s->boxes, stream));
     if (s->normals_on) LAUNCHCHK("normals kernel", launch_normals(s, P, stream, look));
+    if (s->flow_on) LAUNCHCHK("motion-vector kernel", launch_flow(s, P, stream, look, reset_flags, step));
     return LCR_OK;
 }
 
@@ -858,6 +883,7 @@ void lcr_destroy(lcr_sim *s) {
     if (s->height_mem) (void)hipFree(s->height_mem);
     if (s->boxes_mem) (void)hipFree(s->boxes_mem);
     if (s->normals_mem) (void)hipFree(s->normals_mem);
+    if (s->flow_mem) (void)hipFree(s->flow_mem);
     free(s->look_variants);
     if (s->host_mirror) (void)hipHostFree(s->host_mirror);
     (void)hipFree(s->arena);
@@ -936,13 +962,16 @@ int lcr_step(lcr_sim *s, const float *action_dev) {
         // (and the looks, 40 B per env: the redraw of the next step must not reach the frames of this one)
         if (s->look_K) HIPCHK(hipMemcpyAsync(s->snap_look[p], s->look_cur, sizeof(int) * 10 * N, hipMemcpyDeviceToDevice, s->stream));
         // (and did_reset, 1 B per env, for the stack: the step kernel of the next step overwrites the flags while the stack of this one may still have to read them)
+        // (the motion vectors read the same flags: on a handle without a stack the snapshot goes into their own allocation)
+        const unsigned char *flags = s->snap_reset[p];
         if (s->stack_on) HIPCHK(hipMemcpyAsync(s->snap_reset[p], s->dev.did_reset, N, hipMemcpyDeviceToDevice, s->stream));
+        else if (s->flow_on) { HIPCHK(hipMemcpyAsync(s->flow_reset[p], s->dev.did_reset, N, hipMemcpyDeviceToDevice, s->stream)); flags = s->flow_reset[p]; }
         HIPCHK(hipEventRecord(s->ev_snap[p], s->stream));
         HIPCHK(hipStreamWaitEvent(s->rstream, s->ev_snap[p], 0));
         LcrDev R = s->dev;
         R.qpos = s->snap_qpos[p]; R.target = s->snap_target[p];
         // (the stack before ev_rdone: join_render then covers it as it covers the frames)
-        if (int rc = frames_after(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr, s->snap_reset[p], LCR_STACK_PUSH, true)) return rc;
+        if (int rc = frames_after(s, R, s->rstream, s->look_K ? s->snap_look[p] : nullptr, flags, LCR_STACK_PUSH, true)) return rc;
         HIPCHK(hipEventRecord(s->ev_rdone[p], s->rstream));
         s->snap_used[p] = true; s->rpending = true; s->rlast = p; s->rpar = p ^ 1;
     } else if (s->has_images) {   // same stream as the step kernel: did_reset itself is current until the next step
@@ -1084,6 +1113,8 @@ int lcr_set_state(lcr_sim *s, const double *qpos, const double *qvel, const doub
     if (rng) HIPCHK(hipMemcpy(s->dev.rng, rng, 4 * N * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (current_goal) HIPCHK(hipMemcpy(s->dev.goal, current_goal, N * sizeof(int32_t), hipMemcpyHostToDevice));
     if (sim_time) HIPCHK(hipMemcpy(s->dev.sim_time, sim_time, N * sizeof(double), hipMemcpyHostToDevice));
+    // the state has jumped: the motion vectors restart from it (this call draws no frames; the planes are zero and valid is 0 until the next step)
+    if (s->flow_on) LAUNCHCHK("motion-vector kernel", launch_flow(s, s->dev, s->stream, nullptr, nullptr, false));
     return LCR_OK;
 }
 
@@ -2511,6 +2542,86 @@ int lcr_get_normals(lcr_sim *s, lcr_normals_view *out) {
     out->boxes = s->normals.boxes;
     out->camera_pose = s->normals.pose;
     out->bytes_per_env = (uint64_t)s->normals.slots * s->dev.img_w * s->dev.img_h * 4;
+    return LCR_OK;
+}
+
+// ---- the motion vectors ----
+
+int lcr_motion_check(const lcr_motion_spec *spec) {
+    if (!spec) return fail(LCR_ERR_INVALID, "spec is NULL");
+    if (spec->cameras & ~(uint32_t)(LCR_STACK_CAM_FRONT | LCR_STACK_CAM_TOP | LCR_STACK_CAM_WRIST))
+        return fail(LCR_ERR_INVALID, "cameras must be 0 (every camera the handle has) or a mask of 1 (front), 2 (top) and 4 (wrist), got %u", spec->cameras);
+    return LCR_OK;
+}
+
+int lcr_enable_motion_vectors(lcr_sim *s, const lcr_motion_spec *spec) {
+    // the arguments first, the handle afterwards (what can be refused without a device is)
+    if (int rc = lcr_motion_check(spec)) return rc;
+    SIMCHK(s);
+    lcr_motion_spec sp = *spec;
+    if (int rc = planes_ready(s, &sp.cameras, "to give motion vectors to", "the motion vectors need", "the motion vectors")) return rc;
+    if (s->flow_on) {
+        if (sp.cameras == s->flow_spec.cameras) return LCR_OK;
+        return fail(LCR_ERR_INVALID, "motion vectors (cameras %u) are enabled already and fixed for the life of the handle: asked for cameras %u", s->flow_spec.cameras, sp.cameras);
+    }
+    LcrFlow A{};
+    ObsSource src[3];
+    A.slots = sources(s, sp.cameras, src);
+    for (int i = 0; i < A.slots; i++) { A.cam[i] = src[i].cam; A.seg[i] = src[i].seg; A.depth[i] = src[i].depth; }
+    const size_t N = (size_t)s->dev.n, plane = N * s->dev.img_w * s->dev.img_h * 4;
+    // guard, then per slot the plane and a guard (include/lcr.h: LCR_WRIST_GUARD), then the boxes and the camera poses (now, before), valid and the snapshots of did_reset
+    Carver C;
+    C.skip(LCR_WRIST_GUARD);
+    size_t o_plane[3] = {0, 0, 0};
+    for (int i = 0; i < A.slots; i++) { o_plane[i] = C.take(plane); C.skip(LCR_WRIST_GUARD); }
+    const size_t guarded = C.off;
+    const size_t o_boxes = C.take(2 * (size_t)LCR_FLOW_BOXES * LCR_FLOW_BOX_FLOATS * N * sizeof(float));
+    const size_t o_pose = C.take(2 * (size_t)A.slots * 13 * N * sizeof(float));
+    const size_t o_valid = C.take(N);
+    const size_t o_snap[2] = {C.take(N), C.take(N)};
+    A.n = s->dev.n; A.W = s->dev.img_w; A.H = s->dev.img_h;
+    A.ncube = s->dev.task == 4 ? 2 : 1;
+    A.mount = s->wrist.mount;
+    void *mem = nullptr;
+    const int rc = bring_up(s, C, guarded, "the motion vectors", &mem,
+        [&](char *base) {
+            for (int i = 0; i < A.slots; i++) A.out[i] = (unsigned *)(base + o_plane[i]);
+            A.boxes = (float *)(base + o_boxes);
+            A.pose = (float *)(base + o_pose);
+            A.valid = (unsigned char *)(base + o_valid);
+            s->flow = A;
+            return launch_flow(s, s->dev, s->stream, nullptr, nullptr, false);   // a restart: zero planes, valid 0, "before" a copy of "now"
+        },
+        [s] { s->flow = LcrFlow{}; });
+    if (rc == LCR_ERR_UNSUPPORTED) return fail(LCR_ERR_UNSUPPORTED, "the motion-vector kernel is not built for %d cameras at %d x %d", A.slots, A.W, A.H);
+    if (rc) return rc;
+    for (int p = 0; p < 2; p++) s->flow_reset[p] = (unsigned char *)mem + o_snap[p];
+    s->flow_mem = mem;
+    s->flow_spec = sp;
+    s->flow_on = true;
+    return LCR_OK;
+}
+
+int lcr_get_motion_vectors(lcr_sim *s, lcr_motion_view *out) {
+    if (!s || !out) return fail(LCR_ERR_INVALID, "NULL argument");
+    SIMCHK(s);   // (the planes are made behind the frames, on the second stream after a step: the handle's stream waits for them here)
+    memset(out, 0, sizeof *out);
+    if (!s->flow_on) return LCR_OK;
+    out->enabled = 1;
+    out->spec = s->flow_spec;
+    out->slots = s->flow.slots;
+    out->image_width = s->dev.img_w;
+    out->image_height = s->dev.img_h;
+    for (int i = 0; i < s->flow.slots; i++) {
+        const uint16_t *p = (const uint16_t *)s->flow.out[i];
+        if (s->flow.cam[i] == LCR_CLOUD_CAM_FRONT) out->flow_front = p;
+        else if (s->flow.cam[i] == LCR_CLOUD_CAM_TOP) out->flow_top = p;
+        else out->flow_wrist = p;
+    }
+    out->valid = s->flow.valid;
+    out->boxes = s->flow.boxes;
+    out->camera_pose = s->flow.pose;
+    out->bytes_per_env = (uint64_t)s->flow.slots * s->dev.img_w * s->dev.img_h * 4;
     return LCR_OK;
 }
 

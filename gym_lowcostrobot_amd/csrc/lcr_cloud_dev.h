@@ -1,6 +1,6 @@
 // lcr_cloud_dev.h -- the device code the kernels of the depth-plane observations share: the point cloud (lcr_cloud.hip, lcr_cloud_fps.hip, lcr_cloud_crop.hip), the voxel
-// grid (lcr_voxel.hip), the heightmap (lcr_heightmap.hip) and the surface normals (lcr_normals.hip).
-// The small functions are here, each ONCE: the candidate test, the camera in LDS, the pinned point of a pixel (pinned_point), the cell of a point along an axis (cell_axis),
+// grid (lcr_voxel.hip), the heightmap (lcr_heightmap.hip), the surface normals (lcr_normals.hip) and the motion vectors (lcr_flow.hip).
+// The small functions are here, each ONCE: the candidate test, the camera in LDS, the pinned point of a pixel (pinned_point), lcr_arm.h's dot with every step pinned (pinned_dot), the cell of a point along an axis (cell_axis),
 // the float32 colour element and the wave sum.  The long blocks -- pass 1 and the prefix (lcr_cloud_pass1.inc.h), the way from a candidate number to its point
 // (lcr_cloud_point.inc.h) and the cameras of an env (lcr_obs_cameras.inc.h) -- are statement lists that a kernel includes INSIDE its body: as text, not as functions,
 // because the strided kernels then compile to the instructions they had before the farthest-point kernels existed (inlined functions went through the optimiser in another
@@ -65,6 +65,17 @@ __device__ __forceinline__ void pinned_point(unsigned px, unsigned row, float hW
         asm("" : "+v"(q));
         p[k] = q;
     }
+}
+
+// lcr_arm.h's dot, fmaf(a.x, b.x, fmaf(a.y, b.y, a.z b.z)), with every rounded step opaque
+__device__ __forceinline__ float pinned_dot(float ax, float ay, float az, float bx, float by, float bz) {
+    float m = az * bz;
+    asm("" : "+v"(m));
+    float i = __builtin_fmaf(ay, by, m);
+    asm("" : "+v"(i));
+    float d = __builtin_fmaf(ax, bx, i);
+    asm("" : "+v"(d));
+    return d;
 }
 
 // The header's cell of a point along one axis of a grid or a map: u = p - lo, one float32 subtraction; v = u inv, one rounded float32 multiply; inside iff u >= 0 && v < D;

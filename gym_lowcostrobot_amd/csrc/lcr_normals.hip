@@ -24,7 +24,7 @@
 
 #include "../../include/lcr.h"
 #include "lcr_normals.h"
-#include "lcr_cloud_dev.h"      // store_cam, pinned_point and the wrist pose: shared with the cloud kernels, the grid and the map
+#include "lcr_cloud_dev.h"      // store_cam, pinned_point, pinned_dot and the wrist pose: shared with the cloud kernels, the grid and the map
 #include "lcr_opaque_boxes.h"
 
 namespace {
@@ -34,17 +34,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));   // 16 B: four depths
 constexpr int BS = 17;                                    // dwords of a box in LDS: 15 used, an odd stride
 constexpr int TAB = 2 + 6 * LCR_NORMALS_BOXES;            // sky, floor, six faces a box
 constexpr unsigned SETUP = LCR_NORMALS_THREADS - 64;      // the first lane of the last wave
-
-// lcr_arm.h's dot, fmaf(a.x, b.x, fmaf(a.y, b.y, a.z b.z)), with every rounded step opaque
-__device__ __forceinline__ float pinned_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    float m = az * bz;
-    asm("" : "+v"(m));
-    float i = __builtin_fmaf(ay, by, m);
-    asm("" : "+v"(i));
-    float d = __builtin_fmaf(ax, bx, i);
-    asm("" : "+v"(d));
-    return d;
-}
 
 // the header's quantisation of one component: clamp((int)rintf(127 c), -127, 127), as a byte
 __device__ __forceinline__ unsigned quantise(float c) {

@@ -71,6 +71,7 @@ class ShardedVecSim:
         # (heightmap too: every shard keeps the map of its own envs, shards[i].heightmap; its box is in the world frame as well: every shard gets the same spec)
         # (object_boxes too: every shard keeps the records of its own envs, shards[i].object_boxes; an env's records depend on that env's planes alone: the same spec)
         # (surface_normals too: every shard keeps the planes of its own envs, shards[i].normals_front ...; an env's normals depend on that env alone: the same spec)
+        # (motion_vectors too: every shard keeps the planes and the pose history of its own envs, shards[i].flow_front ...; an env's flow depends on that env alone: the same spec)
         # (terminal=True in obs_stack / point_cloud too: obs_stack_terminal() / point_cloud_terminal() below take GLOBAL env ids and ask the shard that owns each)
         # (planes=("depth",) in obs_stack too: the key goes to every shard with the dict, every shard stacks its own depth planes, and the terminal call is routed as before)
         # (image_planes / depth_far, like every other keyword, go to each shard's VecSim: the planes are per-shard device arrays, shards[i].depth_front ...)

@@ -92,6 +92,9 @@ class LowCostRobotVecEnv(_SB3VecEnv):
         if kw.get("surface_normals") not in (None, False):   # (no terminal form: the library has no call that makes the normals of an episode that has ended)
             raise ValueError("surface_normals is for on-device loops over VecSim: an env the step has auto-reset shows its reset state, and the library cannot make the plane of the "
                              "episode that ended, so LowCostRobotVecEnv / LowCostRobotVectorEnv, which owe SB3 / gymnasium a complete terminal_observation, do not expose it")
+        if kw.get("motion_vectors") not in (None, False):   # (no terminal form: the library has no call that makes the motion vectors of an episode that has ended)
+            raise ValueError("motion_vectors is for on-device loops over VecSim: an env the step has auto-reset shows its reset state, and the library cannot make the plane of the "
+                             "episode that ended, so LowCostRobotVecEnv / LowCostRobotVectorEnv, which owe SB3 / gymnasium a complete terminal_observation, do not expose it")
         self.sim = VecSim(task, num_envs, device=device, env_id_offset=env_id_offset, base_seed=seed, auto_reset=True, **kw)
         self.num_envs = int(num_envs)
         self.task = task

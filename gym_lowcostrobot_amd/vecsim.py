@@ -100,6 +100,7 @@ class VecSim:
         heightmap=None,
         object_boxes=None,
         surface_normals=None,
+        motion_vectors=None,
     ):
         self.L = _capi.load()
         if action_mode not in ACTION_MODES:
@@ -230,6 +231,21 @@ class VecSim:
                     raise ValueError(f"surface_normals is made of the depth and the segmentation plane: the {plane} plane is missing, pass both, "
                                      f"image_planes=('depth', 'segmentation') (got {image_planes!r})")
             check(self.L.lcr_normals_check(ctypes.byref(surface_normals)))
+        # the motion vectors (lcr_enable_motion_vectors): None / False = none, True = every camera the handle has, or a dict with cameras.  Checked here and by the library
+        # without a handle (lcr_motion_check), before it is asked for a device.  They are made of the depth and the segmentation plane: neither is switched on silently
+        if motion_vectors is None or motion_vectors is False:
+            motion_vectors = None
+        else:
+            if observation_mode == "state":
+                raise ValueError("motion_vectors needs image observations: observation_mode 'image' or 'both'")
+            motion_vectors = _capi.MotionSpec.from_any(motion_vectors, wrist=wrist_camera is not None)
+            if motion_vectors.cameras & _capi.STACK_CAMERAS["wrist"] and wrist_camera is None:
+                raise ValueError("motion_vectors: cameras selects 'wrist', but no wrist_camera is given")
+            for plane in _capi.IMAGE_PLANES:
+                if plane not in image_planes:
+                    raise ValueError(f"motion_vectors is made of the depth and the segmentation plane: the {plane} plane is missing, pass both, "
+                                     f"image_planes=('depth', 'segmentation') (got {image_planes!r})")
+            check(self.L.lcr_motion_check(ctypes.byref(motion_vectors)))
         self.task_name = task if isinstance(task, str) else {v: k for k, v in TASKS.items()}[task]
         cfg = LcrConfig()
         # preset: "faithful" (the reference's contact model solved by Newton's method) | "fast" (rounds 1-4: four sweeps, fewer rows); None = the library's default
@@ -482,6 +498,22 @@ class VecSim:
                 setattr(self, "normals_" + cam, DeviceArray(self, getattr(nv, "normals_" + cam), (N, int(nv.image_height), int(nv.image_width), 4), np.int8))
             self.normals_boxes = DeviceArray(self, nv.boxes, (_capi.NORMALS_BOXES, _capi.NORMALS_BOX_FLOATS, N), np.float32)
             self.normals_pose = DeviceArray(self, nv.camera_pose, (int(nv.slots), 13, N), np.float32)
+        # the motion vectors: (N, H, W, 2) float16 per selected camera -- current minus previous pixel position --, valid, and the boxes and camera poses the kernel used,
+        # [0] now and [1] before.  A handle without them has none of these attributes
+        if motion_vectors is not None:   # (behind look, wrist camera and planes; independent of every other observation unit; the last launch behind the frames)
+            try:
+                check(self.L.lcr_enable_motion_vectors(self.handle, ctypes.byref(motion_vectors)))
+                mv = _capi.LcrMotionView()
+                check(self.L.lcr_get_motion_vectors(self.handle, ctypes.byref(mv)))
+            except Exception:
+                self.close()
+                raise
+            self.flow_spec = mv.spec.as_dict()
+            for cam in self.flow_spec["cameras"]:
+                setattr(self, "flow_" + cam, DeviceArray(self, getattr(mv, "flow_" + cam), (N, int(mv.image_height), int(mv.image_width), 2), np.float16))
+            self.flow_valid = DeviceArray(self, mv.valid, (N,), np.uint8)
+            self.flow_boxes = DeviceArray(self, mv.boxes, (2, _capi.NORMALS_BOXES, _capi.NORMALS_BOX_FLOATS, N), np.float32)
+            self.flow_pose = DeviceArray(self, mv.camera_pose, (2, int(mv.slots), 13, N), np.float32)
         self.reward = DeviceArray(self, out.reward, (N,), np.float32)
         self.terminated = DeviceArray(self, out.terminated, (N,), np.uint8)
         self.truncated = DeviceArray(self, out.truncated, (N,), np.uint8)
@@ -520,7 +552,7 @@ class VecSim:
 
     def wait_frames(self):
         """make the handle's stream wait -- an event wait on the device, the host goes on -- for whatever the last step is still drawing on the second stream (frames, planes,
-        wrist frames, stack, point cloud, voxel grid, heightmap, object boxes, surface normals): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
+        wrist frames, stack, point cloud, voxel grid, heightmap, object boxes, surface normals, motion vectors): what is enqueued on the handle's stream afterwards reads the observations of that step (lcr_get_obs, a joining call)"""
         check(self.L.lcr_get_obs(self.handle, ctypes.byref(LcrObsView())))
 
     # ---- reset / step ----
@@ -762,6 +794,8 @@ class VecSim:
                 obs["object_boxes"] = self.object_boxes.numpy()
             for cam in getattr(self, "normals_spec", {"cameras": ()})["cameras"]:
                 obs["normals_" + cam] = getattr(self, "normals_" + cam).numpy()
+            for cam in getattr(self, "flow_spec", {"cameras": ()})["cameras"]:
+                obs["flow_" + cam] = getattr(self, "flow_" + cam).numpy()
         if OBS_MODES["state"] == self.cfg.obs_mode or OBS_MODES["both"] == self.cfg.obs_mode:
             obs[self.cube_name] = self.cube_pos.numpy().T.copy()
             if self.task_name == "stack":

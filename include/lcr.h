@@ -1013,6 +1013,83 @@ int lcr_enable_normals(lcr_sim *sim, const lcr_normals_spec *spec);
 /* The planes; waits (on the handle's stream) for frames and normals still being made on the second stream, as every entry point but the step does. */
 int lcr_get_normals(lcr_sim *sim, lcr_normals_view *out);
 
+/* == Motion vectors: optional device buffers per handle, one plane `flow` [N][H][W][2] float16 per selected camera, that the library keeps current behind the frame kernels --
+ * per pixel the BACKWARD optical flow of the surface point the pixel shows: current pixel position minus the position of the same point one control step (one lcr_step) ago,
+ * in pixels, x to the right and y down.  The point pixel (row, px) shows was at (px - fx, row - fy) in the frame of the previous step.  For flow-conditioned policies,
+ * point-track prediction and video-prediction pre-training.  The flow is EXACT, not estimated from two frames: every opaque surface is the floor or one of nine rigid boxes,
+ * the segmentation byte says which, the depth plane gives the point, and the pose snapshots of this step and the previous one give the rigid motion of that box and of the
+ * camera.  One streaming kernel, in stream order, without a host round trip.  Off by default: without lcr_enable_motion_vectors no byte, state, output or kernel of the handle
+ * changes.  It is the one observation with a step of history in its geometry: the stack keeps frames, this keeps poses.
+ *   inputs      as the surface normals: the segmentation and depth planes of the selected camera slots at the configured size [H][W] (`cameras`: LCR_STACK_CAM_* bits, 0 =
+ *               every camera the handle has; slots in the order front, top, wrist; the wrist bit on a handle without a wrist camera is refused), the camera that drew each
+ *               slot and the pose snapshot `qpos` the frames were drawn from -- and the same of the previous step, kept as numbers, never recomputed.
+ *   element     [..., 0] fx and [..., 1] fy as IEEE binary16.
+ *   history     `boxes` [2][9][15][N] and `camera_pose` [2][slots][13][N], [0] NOW and [1] BEFORE, in the layout of the normals' boxes (c, X, Y, Z, h of the nine opaque
+ *               boxes, surface ids 2 .. 10) and camera_pose (ro, X, Y, Z, s): exactly what the kernel used and what a model of the rule reads.  This unit is built without
+ *               -ffast-math (see "the division"), so the sine and cosine behind the wrist pose and the arm boxes may differ in the last bit from what the normals' unit
+ *               computes from the same joints: a model reads THESE arrays, not the normals'.
+ *   valid       [N] uint8: 1 iff the env's planes describe the motion across the last lcr_step and that step did not auto-reset the env.
+ *   bit-equal   a slot is CAMERA-STATIC iff its 13 pose words are bit-equal now and before; box b is STATIC iff its 12 words c, A_0, A_1, A_2 are.  Both compare the uint32
+ *               words, not the floats.
+ *   the rule    for pixel (row, px) of a slot with pose now (ro, X, Y, Z, s) and before (ro', X', Y', Z', s'), id i = seg & 0x7F (the marker bit is ignored), box b = i - 2
+ *               now (c, A_0, A_1, A_2) and before (c', A'_0, A'_1, A'_2).  Every step is ONE float32 operation; dot(a, b) = fmaf(a.x, b.x, fmaf(a.y, b.y, a.z * b.z)).
+ *                 env not valid, or i = 0, or i > 10              (+0.0, +0.0): the sky carries no flow, also under a turning wrist camera
+ *                 i = 1 (the floor), slot camera-static           (+0.0, +0.0), no depth is loaded
+ *                 i = 1, otherwise                                the chain with q = p
+ *                 i = 2 .. 10, box b static, slot camera-static   (+0.0, +0.0), no depth is loaded
+ *                 i = 2 .. 10, otherwise                          the chain
+ *   the chain     hx    = px + 0.5 - W / 2, hy = row + 0.5 - H / 2: exact
+ *                 p     the pinned point of the crop box, the grid, the map and the normals, through the pose NOW and the depth word as stored: per axis
+ *                       fmaf(t, fmaf(sx, X, fmaf(sy, Y, -Z)), ro) with sx = hx s and sy = -(hy s) one rounded multiply each
+ *                 u     = p - c per axis
+ *                 l_k   = dot(u, A_k) for k = 0, 1, 2: the point in the box's own frame
+ *                 q     per axis: fmaf(l_0, A'_0.axis, fmaf(l_1, A'_1.axis, fmaf(l_2, A'_2.axis, c'.axis))): the same point of the box where the box was
+ *                 w     = q - ro' per axis
+ *                 a     = dot(w, X'), b = dot(w, Y'), d = dot(w, Z')
+ *                 den   = (-d) * s'
+ *                 !(den > 0.0f): (+0.0, +0.0) -- a point behind the previous camera; it cannot happen on the fixed cameras
+ *                 gx    = a / den, gy = b / den: ONE correctly rounded float32 division each
+ *                 fx    = hx - gx, fy = hy + gy
+ *                 out   ((half)fx, (half)fy), each rounded to nearest even; an overflow gives what the conversion gives (an infinity)
+ *   the division  under -ffast-math every spelling of a float32 division compiles to a reciprocal and a multiply on gfx950, so the unit of this kernel alone is built with
+ *               -fno-fast-math -ffp-contract=off (gym_lowcostrobot_amd/build.py) and the division is the IEEE one.
+ *   reproducible  every word is a function of its own pixel and the history: nothing depends on the order lanes arrive in.
+ *   invariant   lcr_step is the only entry point that MEASURES: before its kernel "now" becomes "before" (two device-to-device copies, about 700 bytes an env together, on
+ *               the stream the frames run on), the kernel reads only "before" and writes only "now", and valid[env] = !did_reset[env], read from the snapshot of the flags
+ *               the step takes for the stack (taken for the motion vectors too on a handle without a stack).  An env the step has auto-reset has zero planes.
+ *               Every other entry point that draws the batched frames -- lcr_reset with its masked and no-op forms, lcr_set_look, enabling -- and lcr_set_state (which
+ *               draws none, but makes the state jump) RESTARTS every env: the planes are zero, valid is 0, "now" is the current state and "before" a copy of it, so the
+ *               next step is valid.
+ *   ordering    the motion-vector kernel is the last launch behind the frame kernels -- frames, stack, cloud, grid, map, boxes, normals, motion vectors -- on whatever stream
+ *               they ran on; the event the joining entry points wait for is recorded after it.
+ *   life        needs image observations and BOTH planes, neither switched on silently.  Fixed for the life of the handle: the same spec again does nothing, another spec is
+ *               refused, naming both.
+ *   memory      4 bytes per pixel and camera (307 200 bytes per env and camera at 240 x 320); the caller chooses it.  One allocation, laid out as the normals' is:
+ *               LCR_WRIST_GUARD bytes of LCR_WRIST_GUARD_BYTE, then per slot the plane and the same guard from the first 256-byte boundary at or behind its end, then
+ *               boxes, camera_pose, valid and two snapshots of did_reset.  Freed by lcr_destroy; LCR_ERR_OOM if it fails.
+ *   not in it   an occlusion or disocclusion mask, forward flow on the previous frame's grid, scene flow in metres, flow of the sky or of the marker, float32 output,
+ *               terminal planes (there is no _terminal call, so the vector adapters refuse them), the recorder, a flow channel of the stack. */
+typedef struct lcr_motion_spec {
+    uint32_t cameras;                  /* LCR_STACK_CAM_* bits; 0 = every camera the handle has */
+} lcr_motion_spec;
+typedef struct lcr_motion_view {
+    int32_t enabled;                   /* 0: no motion vectors, everything below is 0 / NULL */
+    lcr_motion_spec spec;              /* as enabled, cameras resolved */
+    int32_t slots, image_width, image_height;
+    const uint16_t *flow_front, *flow_top, *flow_wrist;   /* device, [N][H][W][2] binary16; NULL for a camera that is not selected */
+    const uint8_t *valid;              /* device, [N] */
+    const float *boxes;                /* device, [2][9][15][N]: now, before -- c, X, Y, Z, h of the nine boxes */
+    const float *camera_pose;          /* device, [2][slots][13][N]: now, before -- ro, X, Y, Z, s */
+    uint64_t bytes_per_env;            /* slots H W 4 */
+} lcr_motion_view;
+/* The checks lcr_enable_motion_vectors makes of `spec` before it looks at the handle, on their own: LCR_OK, or LCR_ERR_INVALID -- cameras with unknown bits */
+int lcr_motion_check(const lcr_motion_spec *spec);
+/* Switch the motion vectors on.  `spec` is checked first; then a NULL handle, a handle without image observations, one without both planes (naming the missing one) and a
+ * wrist bit without a wrist camera are refused (LCR_ERR_INVALID); an allocation that fails is LCR_ERR_OOM.  Restarts: zero planes, valid 0. */
+int lcr_enable_motion_vectors(lcr_sim *sim, const lcr_motion_spec *spec);
+/* The planes; waits (on the handle's stream) for frames and motion vectors still being made on the second stream, as every entry point but the step does. */
+int lcr_get_motion_vectors(lcr_sim *sim, lcr_motion_view *out);
+
 /* Measurement support: copy n_floats floats from the start of the state arena to dst_dev with one dword load and
  * one dword store per lane (the step kernel's access pattern): a launch with a KNOWN byte count (4*n read, 4*n
  * written) against which rocprofv3 FETCH_SIZE / WRITE_SIZE are calibrated (MI355X_MICROARCH.md, HBM section). */
